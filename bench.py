@@ -12,7 +12,11 @@ all_gather).
          new(1e9, 0.01) = 2^32-1 bits (the saturated u32, src/bloom/mod.rs:49).
 `--gpus N` launched without torchrun starts the N rank processes itself.
 
-Also reported (extra keys on the same JSON line):
+A plain run sets up, warms up, times --steps such steps, writes the last
+step's words if --dump-outputs DIR is given, and prints the headline line.
+
+With --full, also reported (extra keys on the same JSON line), along with the
+oracle-fixture word checks and, for N > 1, the serial split and self-check:
   probe        C3: 10 M 16-B lookup keys x 8 SSTable filters (new(1000, 0.01)), Mkeys/s
   roofline     the build kernels vs 8 TB/s HBM, algorithmic bytes per build
   cpu_baseline the CPU oracle (C restatement of src/bloom, "port") on a bounded sample,
@@ -39,6 +43,15 @@ def parse():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=20)  # ~28 ms of C2 steps: the clock has ramped (tools/archive/r04_warm.sh)
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also run every other leg and check: the per-kernel times and "
+                         "roofline, the oracle-fixture word checks, the N > 1 serial split and single-GPU self-check, "
+                         "the C3 probe, C2 exact, C1, end-to-end, C4, C5 legs and the CPU baseline (each with its "
+                         "--no-* switch).  Without it the run only sets up, warms up, times --steps steps and prints "
+                         "the headline line")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="write what the last timed step computed (the filter words, see dump_outputs) as "
+                         "DIR/<name>.npy")
     ap.add_argument("--global-keys", type=int, default=0,
                     help="keys of the whole run, split over the ranks (default: 1e8 = C2 at N=1, 1e9 = C5 at N>1)")
     ap.add_argument("--keys-per-gpu", type=int, default=0,
@@ -493,8 +506,12 @@ def main():
     dt = max_over_ranks(time.perf_counter() - t0)
     ms = dt / args.steps * 1e3
     value = total * args.steps / dt / 1e6
+    if args.dump_outputs and rank == 0:
+        # the words of the last timed step (N > 1: merged), before any other leg rebuilds them;
+        # barrier() above has synchronised the device
+        dump_outputs(args.dump_outputs, words)
     build_ms = coll_ms = serial_ms = 0.0
-    if world > 1:
+    if world > 1 and args.full:
         # Split (outside the timed region): the same steps run serially —
         # build, then the full-filter OR-allreduce — timed by events.
         ev = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True),
@@ -513,26 +530,28 @@ def main():
         coll_ms = max_over_ranks(sum(b.elapsed_time(c) for _, b, c in ev) / args.steps)
 
     # per-kernel times (HIP events on the build stream), averaged over `steps` builds
-    ctx.set_timing(True)
-    kt = np.zeros(3)
-    for _ in range(args.steps):
-        build()
-        ctx.sync()
-        torch.cuda.synchronize(dev)
-        kt += np.array(ctx.last_build_ms())
-    kt /= args.steps
-    ctx.set_timing(False)
     strategy = lsmbloom.build_strategy(nb, npg, k)
-    alg_bytes = 16 * npg + 8 * nw
-    # C2 at N = 1; a C5 shard (125 M keys into 2^32-1 bits) at N = 8
-    main_leg = {(100_000_000, 956715292): "c2", (125_000_000, 4294967295): "c5"}.get((npg, nb))
-    roof = leg_roofline(main_leg, alg_bytes, kt[0], "build (%s: k_bin + k_apply + k_ovf_apply)" % strategy)
-    roof.update({"algorithmic_bytes_per_key": round(alg_bytes / npg, 3), "pass_a_ms": round(float(kt[1]), 4),
-                 "pass_b_ms": round(float(kt[2]), 4)})
-    if world == 1 and npg == 100_000_000:
-        roof["hash_walk_floor"] = dict(HASH_WALK_FLOOR, frac_of_hbm_roofline_at_that_time=round(
-            alg_bytes / (HASH_WALK_FLOOR["ms"] * 1e-3) / 1e9 / HBM_PEAK_GBS, 4))
-        roof["hash_walk_floor"]["phase"] = PASS_A_PHASE
+    roof = None
+    if args.full:
+        ctx.set_timing(True)
+        kt = np.zeros(3)
+        for _ in range(args.steps):
+            build()
+            ctx.sync()
+            torch.cuda.synchronize(dev)
+            kt += np.array(ctx.last_build_ms())
+        kt /= args.steps
+        ctx.set_timing(False)
+        alg_bytes = 16 * npg + 8 * nw
+        # C2 at N = 1; a C5 shard (125 M keys into 2^32-1 bits) at N = 8
+        main_leg = {(100_000_000, 956715292): "c2", (125_000_000, 4294967295): "c5"}.get((npg, nb))
+        roof = leg_roofline(main_leg, alg_bytes, kt[0], "build (%s: k_bin + k_apply + k_ovf_apply)" % strategy)
+        roof.update({"algorithmic_bytes_per_key": round(alg_bytes / npg, 3), "pass_a_ms": round(float(kt[1]), 4),
+                     "pass_b_ms": round(float(kt[2]), 4)})
+        if world == 1 and npg == 100_000_000:
+            roof["hash_walk_floor"] = dict(HASH_WALK_FLOOR, frac_of_hbm_roofline_at_that_time=round(
+                alg_bytes / (HASH_WALK_FLOOR["ms"] * 1e-3) / 1e9 / HBM_PEAK_GBS, 4))
+            roof["hash_walk_floor"]["phase"] = PASS_A_PHASE
 
     out = {"metric": "bloom build + batched probe, Mkeys/s device-resident, at 1/2/4/8 MI355X",
            "value": round(value, 2), "unit": "Mkeys/s", "n_gpus": world, "steps": args.steps,
@@ -549,7 +568,8 @@ def main():
                       "parallelism": "dp%d" % world}}
     if args.filter_keys:
         out["config"]["filter_sized_for_keys"] = args.filter_keys
-    out["roofline"] = roof
+    if roof is not None:
+        out["roofline"] = roof
     if world > 1:
         moved = 2 * (world - 1) / world * 8 * nw
         out["config"]["backend"] = backend
@@ -574,36 +594,40 @@ def main():
                              "merges_available": list(merges),
                              "or_allreduce_bytes_per_gpu": int(moved),
                              "or_allreduce_GBs_per_gpu": round(moved / (coll_ms * 1e-3) / 1e9, 1) if coll_ms else None}
-        # Self-check (outside the timed region): one more sharded step; rank 0
-        # then rebuilds the whole global key set alone, shard by shard, and
-        # compares every word.  Its build time is the 1-GPU time of this same
-        # workload (C5 on one GPU), for the strong-scaling curve.
-        step()
-        torch.cuda.synchronize(dev)
-        if args.inject_merge_fault and rank == 0:
-            words[nw // 3] ^= 1 << 17  # tests: a merge that lost a bit must invalidate the line
-        if rank == 0:
-            try:
-                ref = torch.zeros_like(words)
-                buf = torch.empty((nmax, 16), dtype=torch.uint8, device=dev)
-                one_ms = 0.0
-                for r in range(world):
-                    a, b = shard(total, world, r) if scaling == "strong" else (r * npg, (r + 1) * npg)
-                    ctx.gen_key16_dev(SEED_MEMBERS, a, b - a, buf[: b - a])
-                    s0, s1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-                    s0.record()
-                    ctx.build_fixed_dev(buf[: b - a], 16, b - a, nb, k, ref)
-                    s1.record()
-                    torch.cuda.synchronize(dev)
-                    one_ms += s0.elapsed_time(s1)
-                ctx.sync()
-                out["multi_gpu_merged_equals_single_gpu_build"] = bool(torch.equal(ref, words))
-                out["single_gpu_same_workload"] = {
-                    "what": "rank 0 alone builds all %d keys into the same filter (build kernels only)" % total,
-                    "ms": round(one_ms, 3), "value": round(total / (one_ms * 1e-3) / 1e6, 2), "unit": "Mkeys/s"}
-                del ref, buf
-            except Exception as e:  # report, never lose the bench line
-                out["multi_gpu_check_error"] = repr(e)[:200]
+        if args.full:
+            # Self-check (outside the timed region): one more sharded step; rank 0
+            # then rebuilds the whole global key set alone, shard by shard, and
+            # compares every word.  Its build time is the 1-GPU time of this same
+            # workload (C5 on one GPU), for the strong-scaling curve.
+            step()
+            torch.cuda.synchronize(dev)
+            if args.inject_merge_fault and rank == 0:
+                words[nw // 3] ^= 1 << 17  # tests: a merge that lost a bit must invalidate the line
+            if rank == 0:
+                try:
+                    ref = torch.zeros_like(words)
+                    buf = torch.empty((nmax, 16), dtype=torch.uint8, device=dev)
+                    one_ms = 0.0
+                    for r in range(world):
+                        a, b = shard(total, world, r) if scaling == "strong" else (r * npg, (r + 1) * npg)
+                        ctx.gen_key16_dev(SEED_MEMBERS, a, b - a, buf[: b - a])
+                        s0, s1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                        s0.record()
+                        ctx.build_fixed_dev(buf[: b - a], 16, b - a, nb, k, ref)
+                        s1.record()
+                        torch.cuda.synchronize(dev)
+                        one_ms += s0.elapsed_time(s1)
+                    ctx.sync()
+                    out["multi_gpu_merged_equals_single_gpu_build"] = bool(torch.equal(ref, words))
+                    out["single_gpu_same_workload"] = {
+                        "what": "rank 0 alone builds all %d keys into the same filter (build kernels only)" % total,
+                        "ms": round(one_ms, 3), "value": round(total / (one_ms * 1e-3) / 1e6, 2), "unit": "Mkeys/s"}
+                    del ref, buf
+                except Exception as e:  # report, never lose the bench line
+                    out["multi_gpu_check_error"] = repr(e)[:200]
+        else:  # no serial split was run: its figures are not in the line
+            for key in ("build_ms", "or_allreduce_ms", "what", "serial_ms_per_step", "or_allreduce_GBs_per_gpu"):
+                del out["step_split"][key]
         if ipc:
             torch.cuda.synchronize(dev)
             poisoned, tmo = ipc.status()
@@ -617,7 +641,7 @@ def main():
     # Full-size parity in the bench line itself: the filter the timed steps built
     # (N = 1: C2; N > 1: the merged C5 filter on rank 0) against the oracle's
     # committed digest.  Outside the timed region.
-    if rank == 0 and not args.filter_keys and scaling == "strong":
+    if args.full and rank == 0 and not args.filter_keys and scaling == "strong":
         name = {100_000_000: "c2", 1_000_000_000: "c5"}.get(total)
         if name:
             torch.cuda.synchronize(dev)
@@ -640,27 +664,29 @@ def main():
         ref = orc.build_fixed_mt(host, 16, nb, k, 16)
         out["verified_bit_exact"] = bool(np.array_equal(words.cpu().numpy().view(np.uint64), ref))
 
-    if not args.no_probe:
+    # Every other leg runs under --full only (each with its own --no-* switch).
+    one = args.full and world == 1
+    if args.full and not args.no_probe:
         out["probe"] = bench_probe(ctx, dev, args, world, rank, max_over_ranks)
-    if world == 1 and not args.no_exact10:
+    if one and not args.no_exact10:
         out["c2_exact_10_bits_per_key"] = bench_exact10(ctx, keys, npg)
-    if world == 1 and not args.no_c1:
+    if one and not args.no_c1:
         out["c1_gpu"] = bench_c1_gpu(ctx, dev)
-    if not args.no_e2e and rank == 0 and world == 1:
+    if one and not args.no_e2e and rank == 0:
         out["e2e"] = bench_e2e(ctx, keys, npg, nb, k)
 
     del keys
     words = None
     torch.cuda.empty_cache()
-    if not args.no_varlen and world == 1:
+    if one and not args.no_varlen:
         out["varlen"] = bench_varlen(ctx, dev, args)
-    if not args.no_c5 and world == 1:
+    if one and not args.no_c5:
         out["c5_shard"] = bench_c5_shard(ctx, dev)
         torch.cuda.empty_cache()
-    if not args.no_c5_full and world == 1:
+    if one and not args.no_c5_full:
         out["c5_full"] = bench_c5_full(ctx, dev)
         torch.cuda.empty_cache()
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if one and rank == 0 and not args.no_cpu_baseline:
         out["cpu_baseline"] = cpu_baseline(nb, k, args.cpu_seconds)
         out["cpu_baseline"]["gpu_over_cpu_1thread"] = round(value / out["cpu_baseline"]["value"], 1)
     if rank == 0:
@@ -677,6 +703,36 @@ def main():
         dist.destroy_process_group()
     if out.get("invalid"):
         sys.exit(3)
+
+
+DUMP_SEED = 0xD0A7
+DUMP_SAMPLE_WORDS = 2_000_000
+DUMP_BLOCK_WORDS = 16
+
+
+def dump_outputs(outdir, words):
+    """--dump-outputs: the filter words the last timed step left (what a caller
+    of the build receives), as float32 arrays that hold their integers exactly,
+    44 MB for C2, the same files for the same arguments:
+      words_sample_u16.npy  [S, 5]: S = min(nw, DUMP_SAMPLE_WORDS) word indices drawn without
+                            replacement by numpy's default_rng(DUMP_SEED), ascending; per row the
+                            word's four 16-bit quarters (least significant first), then its index
+                            modulo 2^16 (which words were drawn is a function of nw alone)
+      words_popcount.npy    [ceil(nw / DUMP_BLOCK_WORDS)]: the set bits of every block of
+                            DUMP_BLOCK_WORDS consecutive words, over the whole filter"""
+    import numpy as np
+    os.makedirs(outdir, exist_ok=True)
+    w = np.ascontiguousarray(words.cpu().numpy().view(np.uint64))
+    nw = w.size
+    idx = np.sort(np.random.default_rng(DUMP_SEED).choice(nw, size=min(nw, DUMP_SAMPLE_WORDS), replace=False))
+    rows = np.empty((idx.size, 5), dtype=np.float32)
+    rows[:, :4] = w[idx].astype("<u8").view("<u2").reshape(-1, 4)
+    rows[:, 4] = idx % 65536
+    np.save(os.path.join(outdir, "words_sample_u16.npy"), rows)
+    pc = np.zeros(-(-nw // DUMP_BLOCK_WORDS) * DUMP_BLOCK_WORDS, dtype=np.uint16)
+    pc[:nw] = np.bitwise_count(w)
+    np.save(os.path.join(outdir, "words_popcount.npy"),
+            pc.reshape(-1, DUMP_BLOCK_WORDS).sum(axis=1, dtype=np.uint32).astype(np.float32))
 
 
 def invalid_reasons(out, timed_merge=None):
@@ -755,7 +811,8 @@ def compact_line(out):
         r["hash_walk_floor_ms"] = {k: hw.get(k) for k in ("ms", "pass_a_geometry_ms", "with_claims_and_slot_writes_ms")}
         if "phase" in hw:
             r["pass_a_phase"] = {k: v for k, v in hw["phase"].items() if k != "source"}
-    c["roofline"] = r
+    if roof:  # --full
+        c["roofline"] = r
     for k in ("invalid", "words_equal_oracle_fixture", "multi_gpu_merged_equals_single_gpu_build",
               "multi_gpu_check_error", "verified_bit_exact", "speedup_vs_single_gpu_same_workload"):
         if k in out:

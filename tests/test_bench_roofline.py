@@ -81,6 +81,37 @@ def test_compact_line_fits_the_driver_tail():
     assert c["legs"]["c3_probe"]["answers_equal_oracle_fixture"] is True
 
 
+def test_dump_outputs_holds_the_words_exactly(tmp_path):
+    """--dump-outputs: float32 files that hold the words' integers exactly (the
+    sampled words' 16-bit quarters and their indices, every block's popcount),
+    the same files for the same words, and another file for one flipped bit."""
+    import numpy as np
+    import torch
+    rng = np.random.default_rng(7)
+    w = rng.integers(0, 2 ** 64, size=100_003, dtype=np.uint64)  # no multiple of the block; fewer than the sample
+    bench.dump_outputs(str(tmp_path / "a"), torch.from_numpy(w.view(np.int64)))
+    bench.dump_outputs(str(tmp_path / "b"), torch.from_numpy(w.view(np.int64)))
+    s = np.load(tmp_path / "a" / "words_sample_u16.npy")
+    pc = np.load(tmp_path / "a" / "words_popcount.npy")
+    assert s.dtype == np.float32 and pc.dtype == np.float32
+    assert s.shape == (w.size, 5) and np.array_equal(s[:, 4], np.arange(w.size) % 65536)
+    q = s[:, :4].astype(np.uint64)
+    assert np.array_equal(q[:, 0] | q[:, 1] << 16 | q[:, 2] << 32 | q[:, 3] << 48, w)
+    assert pc.size == -(-w.size // bench.DUMP_BLOCK_WORDS) and pc.sum(dtype=np.float64) == np.bitwise_count(w).sum()
+    assert pc[-1] == np.bitwise_count(w[-(w.size % bench.DUMP_BLOCK_WORDS):]).sum()
+    for name in ("words_sample_u16.npy", "words_popcount.npy"):
+        assert (tmp_path / "a" / name).read_bytes() == (tmp_path / "b" / name).read_bytes()
+    w[50_000] ^= np.uint64(1) << np.uint64(63)
+    bench.dump_outputs(str(tmp_path / "c"), torch.from_numpy(w.view(np.int64)))
+    assert not np.array_equal(np.load(tmp_path / "c" / "words_popcount.npy"), pc)
+    assert not np.array_equal(np.load(tmp_path / "c" / "words_sample_u16.npy"), s)
+    # a filter larger than the sample: DUMP_SAMPLE_WORDS distinct ascending indices, within 64 MB
+    big = np.zeros(bench.DUMP_SAMPLE_WORDS + 12_345, dtype=np.int64)
+    bench.dump_outputs(str(tmp_path / "d"), torch.from_numpy(big))
+    s = np.load(tmp_path / "d" / "words_sample_u16.npy")
+    assert s.shape == (bench.DUMP_SAMPLE_WORDS, 5) and s.nbytes < 64 * 2 ** 20
+
+
 def test_invalid_reasons():
     """VERDICT r05 item 1 / ADVICE r05: a line whose own checks fail publishes no
     number — bench.invalid_reasons lists why, main() then sets value null and

@@ -365,7 +365,8 @@ def test_bench_pipelined_steps(backend):
     word, with either merge."""
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--backend", backend,
            "--global-keys", "8000000", "--filter-keys", "1000000000", "--steps", "4", "--warmup", "2",
-           "--step-form", "pipelined", "--no-cpu-baseline", "--no-e2e", "--no-varlen", "--no-exact10", "--no-probe"]
+           "--step-form", "pipelined", "--full", "--no-cpu-baseline", "--no-e2e", "--no-varlen", "--no-exact10",
+           "--no-probe"]
     env = dict(os.environ)
     env.pop("WORLD_SIZE", None)
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=300, env=env)
@@ -384,7 +385,7 @@ def test_bench_launches_its_own_ranks(filter_keys, backend):
     over gloo, both on cuda:0.  The line must say n_gpus 2, carry the split
     build / OR-allreduce timing, and the rank-0 word-for-word self-check."""
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--backend", backend,
-           "--global-keys", "8000000", "--steps", "3", "--warmup", "1", "--no-cpu-baseline", "--no-e2e",
+           "--global-keys", "8000000", "--steps", "3", "--warmup", "1", "--full", "--no-cpu-baseline", "--no-e2e",
            "--no-varlen", "--no-exact10", "--probe-keys", "200000"]
     if filter_keys:  # C5's 2^32-1-bit filter: 2 sweeps, per-range allreduce overlapped
         cmd += ["--filter-keys", str(filter_keys), "--no-probe"]
@@ -437,7 +438,7 @@ def test_bench_under_torch_distributed_run():
     base = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2",
             "--master-addr", "127.0.0.1", "--master-port", str(port), os.path.join(ROOT, "bench.py"), "--gpus", "2",
             "--global-keys", "8000000", "--filter-keys", "1000000000", "--steps", "3", "--warmup", "2",
-            "--no-cpu-baseline", "--no-e2e", "--no-varlen", "--no-exact10", "--no-probe"]
+            "--full", "--no-cpu-baseline", "--no-e2e", "--no-varlen", "--no-exact10", "--no-probe"]
     env = dict(os.environ)
     for v in ("WORLD_SIZE", "RANK", "LOCAL_RANK"):
         env.pop(v, None)
@@ -464,7 +465,7 @@ def test_bench_fault_nulls_the_value():
     --inject-merge-fault) must not publish a throughput: value null, the
     reasons in `invalid`, and a non-zero exit after the line."""
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--backend", "gloo",
-           "--global-keys", "2000000", "--steps", "2", "--warmup", "1", "--no-cpu-baseline", "--no-e2e",
+           "--global-keys", "2000000", "--steps", "2", "--warmup", "1", "--full", "--no-cpu-baseline", "--no-e2e",
            "--no-varlen", "--no-exact10", "--no-probe", "--inject-merge-fault"]
     env = dict(os.environ)
     env.pop("WORLD_SIZE", None)
@@ -485,7 +486,8 @@ def test_bench_auto_drops_a_poisoned_ipc_merge():
     passes the word check."""
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--backend", "auto-gloo",
            "--global-keys", "2000000", "--filter-keys", "1000000000", "--steps", "2", "--warmup", "1",
-           "--no-cpu-baseline", "--no-e2e", "--no-varlen", "--no-exact10", "--no-probe", "--inject-ipc-poison"]
+           "--full", "--no-cpu-baseline", "--no-e2e", "--no-varlen", "--no-exact10", "--no-probe",
+           "--inject-ipc-poison"]
     env = dict(os.environ)
     env.pop("WORLD_SIZE", None)
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=300, env=env)

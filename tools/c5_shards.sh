@@ -5,7 +5,7 @@
 cd "${GRAFT_REPO_ROOT:-/root/repo}"
 mkdir -p gpurun_out
 for n in 125000000 250000000 500000000; do
-  env "$@" timeout -k 10 120 python bench.py --steps 5 --warmup 2 --global-keys $n --filter-keys 1000000000 \
+  env "$@" timeout -k 10 120 python bench.py --full --steps 5 --warmup 2 --global-keys $n --filter-keys 1000000000 \
       --no-probe --no-e2e --no-varlen --no-exact10 --no-cpu-baseline > gpurun_out/c5_$n.json || exit $?
   python3 -c "
 import json; d=json.load(open('gpurun_out/c5_$n.json')); r=d['roofline']

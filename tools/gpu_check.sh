@@ -16,7 +16,9 @@ rc=$?
 echo "tests rc=$rc"
 tail -3 gpurun_out/${TAG}_tests.log
 if [ $rc -ne 0 ] && [ $rc -ne 1 ]; then exit $rc; fi
-timeout -k 10 300 python bench.py --steps 10 --warmup 3 > gpurun_out/${TAG}_bench.json 2> gpurun_out/${TAG}_bench.err
+LOGS=${LOGS:-logs}  # where the bench line and its stderr go
+mkdir -p "$LOGS"
+timeout -k 10 300 python bench.py --full --steps 10 --warmup 3 > "$LOGS/${TAG}_bench.json" 2> "$LOGS/${TAG}_bench.err"
 brc=$?
 echo "bench rc=$brc"
 exit $brc

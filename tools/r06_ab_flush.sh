@@ -15,7 +15,7 @@ rc=$?; echo "parity rc=$rc"; tail -3 $OUT/parity_$V.log
 for rep in 1 2 3; do
   for v in base $V; do
     lib=storage-engine_amd/lib/liblsmbloom_$v.so; [ $v = base ] && lib=storage-engine_amd/lib/liblsmbloom.so
-    LSMB_LIB=$PWD/$lib timeout -k 10 200 python bench.py --steps 20 --warmup 10 --no-probe --no-e2e --no-cpu-baseline \
+    LSMB_LIB=$PWD/$lib timeout -k 10 200 python bench.py --full --steps 20 --warmup 10 --no-probe --no-e2e --no-cpu-baseline \
       --no-varlen --no-exact10 --no-c1 --no-c5-full --detail-out $OUT/detail_$v.json > $OUT/b_$v.json 2> $OUT/b_$v.err || { echo "bench $v failed"; exit 1; }
     python3 -c "
 import json; d=json.load(open('$OUT/b_$v.json')); c=d['legs']['c5_shard']; r=d['roofline']

@@ -7,7 +7,7 @@ OUT=$REPO/gpurun_out/${1:-r06e}
 mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
 timeout -k 10 600 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/prof -o run -- \
-  python3 $REPO/bench.py --detail-out $OUT/bench_detail.json > $OUT/bench.json 2> $OUT/bench.err
+  python3 $REPO/bench.py --full --detail-out $OUT/bench_detail.json > $OUT/bench.json 2> $OUT/bench.err
 rc=$?; echo "bench under rocprof rc=$rc"; head -c 400 $OUT/bench.json; echo
 [ $rc -eq 0 ] || exit $rc
 cp $OUT/prof/run_kernel_stats.csv $OUT/kernel_stats.csv 2>/dev/null || find $OUT/prof -name "*kernel_stats.csv" -exec cp {} $OUT/kernel_stats.csv \;

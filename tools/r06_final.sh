@@ -11,6 +11,6 @@ rc=$?; echo "tests rc=$rc"; tail -3 $OUT/tests.log
 timeout -k 10 300 python -c "import __graft_entry__ as g; g.smoke()" > $OUT/smoke.log 2>&1
 rc=$?; echo "smoke rc=$rc"; tail -2 $OUT/smoke.log
 [ $rc -eq 0 ] || exit $rc
-timeout -k 10 400 python bench.py > $OUT/bench.json 2> $OUT/bench.err
+timeout -k 10 400 python bench.py --full > $OUT/bench.json 2> $OUT/bench.err
 rc=$?; echo "bench rc=$rc"; head -c 300 $OUT/bench.json; echo
 exit $rc

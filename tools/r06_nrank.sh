@@ -6,7 +6,7 @@ cd "${GRAFT_REPO_ROOT:-/root/repo}"
 OUT=gpurun_out/${1:-r06q}
 mkdir -p $OUT
 for n in 2 4 8; do
-  timeout -k 10 300 python bench.py --gpus $n --backend ipc --no-cpu-baseline \
+  timeout -k 10 300 python bench.py --full --gpus $n --backend ipc --no-cpu-baseline \
     --detail-out $OUT/n${n}_detail.json > $OUT/n${n}.json 2> $OUT/n${n}.err
   rc=$?
   echo "n=$n rc=$rc"

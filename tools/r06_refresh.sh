@@ -15,7 +15,7 @@ tail -3 $OUT/probe_scale.jsonl
 fi
 timeout -k 10 600 bash tools/run_variants.sh --no-probe --no-c1 --no-c5 --no-c5-full -- base abl1 abl8 abl16 base abl1 abl8 abl16 > $OUT/ablations.log 2>&1 || { echo "ablations failed"; cat $OUT/ablations.log; exit 1; }
 cat $OUT/ablations.log
-LSMB_LIB=$PWD/storage-engine_amd/lib/liblsmbloom_stamp.so timeout -k 10 200 python bench.py --steps 10 --warmup 5 --no-probe \
+LSMB_LIB=$PWD/storage-engine_amd/lib/liblsmbloom_stamp.so timeout -k 10 200 python bench.py --full --steps 10 --warmup 5 --no-probe \
   --no-e2e --no-cpu-baseline --no-varlen --no-exact10 --no-c1 --no-c5 --no-c5-full > $OUT/stamp_bench.json 2> $OUT/stamps.log
 rc=$?; [ $rc -eq 0 ] || [ $rc -eq 3 ] || { echo "stamp run failed"; exit 1; }
 grep "\[stamp\]" $OUT/stamps.log | tail -3

@@ -29,7 +29,7 @@ if [ "$K" != "none" ]; then
   tail -5 $OUT/tests.log
   if [ $rc -ne 0 ] && [ $rc -ne 1 ]; then exit $rc; fi
 fi
-timeout -k 10 400 python bench.py --detail-out $OUT/bench_detail.json > $OUT/bench.json 2> $OUT/bench.err
+timeout -k 10 400 python bench.py --full --detail-out $OUT/bench_detail.json > $OUT/bench.json 2> $OUT/bench.err
 brc=$?
 echo "bench rc=$brc"
 head -c 600 $OUT/bench.json

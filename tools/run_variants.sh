@@ -11,7 +11,7 @@ for v in "$@"; do
   [ "$v" = base ] && lib=$REPO/storage-engine_amd/lib/liblsmbloom.so
   # (exit 3: the line is invalid because its words fail the oracle check, as
   # an ablation's do by construction; its timings still stand for the A/B)
-  out=$(LSMB_LIB=$lib timeout -k 10 120 python3 $REPO/bench.py --steps 20 --warmup 5 --no-e2e \
+  out=$(LSMB_LIB=$lib timeout -k 10 120 python3 $REPO/bench.py --full --steps 20 --warmup 5 --no-e2e \
         --no-cpu-baseline --no-varlen --no-exact10 "${args[@]}")
   rc=$?
   if [ $rc -ne 0 ] && [ $rc -ne 3 ]; then echo "variant $v failed (rc $rc)"; exit 1; fi

@@ -9,7 +9,7 @@ for v in "$@"; do
   lib=$REPO/storage-engine_amd/lib/liblsmbloom_$v.so
   [ "$v" = base ] && lib=$REPO/storage-engine_amd/lib/liblsmbloom.so
   det=$REPO/gpurun_out/varlen_$v.json
-  LSMB_LIB=$lib timeout -k 10 180 python3 $REPO/bench.py --steps 10 --warmup 3 --no-e2e \
+  LSMB_LIB=$lib timeout -k 10 180 python3 $REPO/bench.py --full --steps 10 --warmup 3 --no-e2e \
         --no-cpu-baseline --no-probe --no-exact10 --no-c5-full --no-c5 --no-c1 --detail-out $det > /dev/null
   rc=$?
   if [ $rc -ne 0 ] && [ $rc -ne 3 ]; then echo "variant $v failed (rc $rc)"; exit 1; fi

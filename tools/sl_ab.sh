@@ -4,9 +4,9 @@
 cd "${GRAFT_REPO_ROOT:-/root/repo}"
 mkdir -p gpurun_out
 for env in LSMB_SLICE_LOG2=20 LSMB_SLICE_LOG2=21; do
-  env $env timeout -k 10 120 python bench.py --steps 5 --warmup 2 --no-probe --no-e2e --no-varlen --no-cpu-baseline \
+  env $env timeout -k 10 120 python bench.py --full --steps 5 --warmup 2 --no-probe --no-e2e --no-varlen --no-cpu-baseline \
       > gpurun_out/sl_ab_a.json || exit $?
-  env $env timeout -k 10 120 python bench.py --steps 5 --warmup 2 --no-probe --no-e2e --no-varlen --no-cpu-baseline \
+  env $env timeout -k 10 120 python bench.py --full --steps 5 --warmup 2 --no-probe --no-e2e --no-varlen --no-cpu-baseline \
       --no-exact10 --filter-keys 200000000 > gpurun_out/sl_ab_b.json || exit $?
   python3 -c "
 import json; a=json.load(open('gpurun_out/sl_ab_a.json')); b=json.load(open('gpurun_out/sl_ab_b.json'))

@@ -10,7 +10,7 @@ for v in product abl16 abl1; do
   lib=$REPO/storage-engine_amd/lib/liblsmbloom.so
   [ $v != product ] && lib=$REPO/storage-engine_amd/lib/liblsmbloom_$v.so
   LSMB_LIB=$lib timeout -s KILL 120 rocprofv3 --pmc WRITE_SIZE --output-format csv -d "$OUT/$v" -o run -- \
-    python3 $REPO/bench.py --steps 4 --warmup 1 --no-cpu-baseline --no-e2e --no-varlen --no-exact10 --no-probe \
+    python3 $REPO/bench.py --full --steps 4 --warmup 1 --no-cpu-baseline --no-e2e --no-varlen --no-exact10 --no-probe \
     > "$OUT/$v.log" 2>&1 || exit $?
   python3 - "$OUT/$v/run_counter_collection.csv" $v <<'PY'
 import csv, sys, collections
