@@ -10,7 +10,8 @@
 // (bit p of u64 word p/64 == bit p%32 of u32 word p/32).  OR is associative,
 // commutative and idempotent, so any key order / partition gives identical bits.
 //
-// Strategies (pick_build_strategy):
+// Strategies (chosen by pick_build_strategy, build_plan.hip; launch_build at the
+// bottom of this file runs the one it is given):
 //   Lds        whole filter fits one CU's LDS (<= 160 KiB): every workgroup
 //              builds a private copy with ds_or, then ORs non-zero words into
 //              HBM with one global atomic per word.
@@ -846,380 +847,287 @@ void launch_hash_var(const VarLen& src, uint64_t n, Out out, hipStream_t st) {
     k_hash_var<0, LSMB_HV_KEYS, LSMB_HV_WIN, LSMB_HV_WPE, Out><<<dim3((uint32_t)g), dim3(LSMB_HV_KEYS), 0, st>>>(src.d, src.o, n, out);
 }
 
+// ---------------------------------------------------------------- launchers
+// What the launchers of one launch_build call share.  Each launcher records t1
+// after its first pass and completes `done`: by its last kernel's own dispatch
+// (launch_done) where the path ends in one, with an event record otherwise.
+struct Launch {
+    uint64_t n;
+    uint32_t num_bits, k, nw32;
+    Mod32 md;
+    uint32_t* gw;
+    const PartitionWorkspace& ws;
+    int num_cus;
+    hipStream_t st;
+    BuildTimers* tm;
+    hipEvent_t done;
+    PartitionPlan pl;  // Partition builds
+    TiledPlan tp;      // Tiled builds
+    void record_t1() const {
+        if (tm) hipEventRecord(tm->t1, st);
+    }
+    hipError_t record_done() const { return done ? hipEventRecord(done, st) : hipSuccess; }
+};
+
+// (h1, h2) of every key into `out` (OutH128 / OutRec records).
+template <class Src, class Out>
+hipError_t launch_hash(const Src& src, uint64_t n, Out out, hipStream_t st) {
+    const uint64_t g = (n + 255) / 256;
+    if (g > 0x7FFFFFFFull) return hipErrorInvalidValue;
+    if constexpr (std::is_same<Src, VarLen>::value)
+        launch_hash_var(src, n, out, st);
+    else
+        k_hash<Src, Out><<<dim3((uint32_t)g), dim3(256), 0, st>>>(src, n, out);
+    return hipSuccess;
+}
+
+template <class Src>
+hipError_t launch_lds(const Src& src, const Launch& L) {
+    const size_t smem = (size_t)L.nw32 * 4;
+    // ~8 Ki keys per workgroup keeps the final per-word OR cheap.
+    uint64_t g = (L.n + 8191) / 8192;
+    const uint64_t gmax = (uint64_t)L.num_cus * (smem <= 40 * 1024 ? 4 : 1);
+    if (g > gmax) g = gmax;
+    if (g < 1) g = 1;
+    set_max_lds((const void*)k_build_lds<Src>);
+    k_build_lds<Src><<<dim3((uint32_t)g), dim3(1024), smem, L.st>>>(src, L.n, L.md, L.k, L.nw32, L.gw);
+    L.record_t1();
+    return L.record_done();
+}
+
+template <class Src>
+hipError_t launch_tiled(const Src& src, const Launch& L) {
+    const TiledPlan& tp = L.tp;
+    uint32_t* tiles = reinterpret_cast<uint32_t*>(L.ws.regions);
+    auto tile = [&](auto keys) {
+        using K = decltype(keys);
+        set_max_lds((const void*)k_build_tiled<K>);
+        k_build_tiled<K><<<dim3(tp.chunks * tp.nslices), dim3(1024), kSliceWords32 * 4, L.st>>>(
+            keys, L.n, L.md, L.k, tp.nslices, L.nw32, tp.stride32, tiles);
+    };
+    if (L.ws.hashes) {
+        // every slice's workgroups re-read the keys: hash them once into
+        // 16-B records (L2/MALL-resident at these sizes) and tile over those
+        const hipError_t e = launch_hash(src, L.n, OutH128(L.ws.hashes), L.st);
+        if (e != hipSuccess) return e;
+        tile(Hashed{L.ws.hashes});
+    } else {
+        tile(src);
+    }
+    L.record_t1();
+    return launch_or_reduce(L.gw, tiles, L.nw32, tp.chunks, tp.stride32, L.st, L.done);
+}
+
+template <class Src>
+hipError_t launch_atomic(const Src& src, const Launch& L) {
+    uint64_t g = (L.n + 255) / 256;
+    if (g > (uint64_t)L.num_cus * 8) g = (uint64_t)L.num_cus * 8;
+    k_build_atomic<Src><<<dim3((uint32_t)g), dim3(256), 0, L.st>>>(src, L.n, L.md, L.k, L.gw);
+    L.record_t1();
+    return L.record_done();
+}
+
+// Pass A's position walk: 32-bit remainders, 64-bit, or the folds of the
+// saturated 2^32-1-bit filter (C5) in place of reductions.
+enum class WalkKind { W32, W64, Fold };
+
 template <class W>
-struct WalkTag {  // a walk type as a value (dispatch lambdas)
+struct WalkTag {  // a walk type as a value
     using type = W;
 };
 
 template <class Src>
-hipError_t build_with(const Src& src, uint64_t n, uint32_t num_bits, uint32_t k, uint32_t* gw,
-                      BuildStrategy s, const PartitionWorkspace& ws, int num_cus, hipStream_t st,
-                      BuildTimers* tm, int sweep, bool fresh, bool t0_done = false, hipEvent_t done = nullptr) {
-    // `done` is completed by the last kernel's own dispatch where the path ends
-    // in one (launch_done); otherwise recorded after it.
-    bool done_set = false;
-    const Mod32 md = Mod32::make(num_bits);
-    // sweep >= 0 (partition builds): only that sweep's slices — pass A keeps
-    // their positions, pass B applies them; every other strategy has one sweep
-    if (sweep > 0 && s != BuildStrategy::Partition) return done ? hipEventRecord(done, st) : hipSuccess;
+using BinKernel = void (*)(Src, uint64_t, Mod32, uint32_t, PassA);
+
+// The k_bin instantiation of a pass A launch: exact k = 7 kernels (BloomFilter::new
+// at fpr 0.01) per walk, bin width, whole-filter sweep, keys per lane and LIST
+// form; the rest by k's size class.  ks::Recs replays the walks from records
+// (which hold the saturated filter's folds already: the 64-bit record walk).
+template <class Src>
+BinKernel<Src> pick_k_bin(uint32_t k, WalkKind walk, bool full, bool two, uint32_t sl, bool list) {
+    constexpr bool kRec = std::is_same<Src, ks::Recs>::value;
+    using W32 = std::conditional_t<kRec, RecWalk32, Walk32>;
+    using W64 = std::conditional_t<kRec, RecWalk64, Walk64>;
+    using WFold = std::conditional_t<kRec, RecWalk64, WalkM>;
+    auto k7 = [&](auto wtag, auto slc) -> BinKernel<Src> {
+        using W = typename decltype(wtag)::type;
+        constexpr int SL = decltype(slc)::value;
+        if (list) return full ? k_bin<Src, W, 7, true, true, 1, SL, true> : k_bin<Src, W, 7, true, false, 1, SL, true>;
+        if (full) return two ? k_bin<Src, W, 7, true, true, 2, SL> : k_bin<Src, W, 7, true, true, 1, SL>;
+        return two ? k_bin<Src, W, 7, true, false, 2, SL> : k_bin<Src, W, 7, true, false, 1, SL>;
+    };
+    auto k7w = [&](auto wtag) {
+        return sl == 21 ? k7(wtag, std::integral_constant<int, 21>{}) : k7(wtag, std::integral_constant<int, kSliceLog2>{});
+    };
+    if (k == 7) {
+        if (walk == WalkKind::W32) return k7w(WalkTag<W32>{});
+        return walk == WalkKind::Fold ? k7w(WalkTag<WFold>{}) : k7w(WalkTag<W64>{});
+    }
+    const bool w32 = walk == WalkKind::W32;
+    if (k <= 8) return w32 ? k_bin<Src, W32, 8, false, false> : k_bin<Src, W64, 8, false, false>;
+    if (k <= 16) return w32 ? k_bin<Src, W32, 16, false, false> : k_bin<Src, W64, 16, false, false>;
+    return w32 ? k_bin<Src, W32, 32, false, false> : k_bin<Src, W64, 32, false, false>;
+}
+
+// Pass A's arguments for sweep sw (PassA's field order).
+PassA pass_a_args(const Launch& L, uint32_t sw) {
+    const PartitionPlan& pl = L.pl;
+    const PartitionWorkspace& ws = L.ws;
+    const uint32_t b0 = sw * pl.bins_per_sweep;
+    return PassA{b0, std::min<uint32_t>(pl.bins_per_sweep, pl.nbins - b0), pl.nbins, pl.grid, pl.cap_segs, pl.ring,
+                 ws.regions, ws.counts, L.gw, ws.ovf, ws.dirty,
+                 ws.ovl + (uint64_t)sw * pl.grid * kOvfListCap,  // one list per workgroup per sweep
+                 ws.ovn + (uint64_t)sw * pl.grid, kOvfListCap, ws.err};
+}
+
+#if LSMB_STAMP
+void report_stamp(hipStream_t st) {
+    unsigned long long h[8];
+    hipStreamSynchronize(st);
+    hipMemcpyFromSymbol(h, HIP_SYMBOL(g_stamp), sizeof h);
+    const double ph = (double)h[4] ? (double)h[4] : 1.0;  // wave-phases
+    const double tot = (double)(h[0] + h[1] + h[2] + h[3]);
+    fprintf(stderr, "[stamp] waves %llu phases/wave %.1f cycles/phase %.0f: work %.0f (%.1f%%) b1 %.0f (%.1f%%) "
+                    "flush %.0f (%.1f%%) b2 %.0f (%.1f%%)\n",
+            h[5], ph / (double)h[5], tot / ph, h[0] / ph, 100 * h[0] / tot, h[1] / ph, 100 * h[1] / tot,
+            h[2] / ph, 100 * h[2] / tot, h[3] / ph, 100 * h[3] / tot);
+    const unsigned long long z[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    hipMemcpyToSymbol(HIP_SYMBOL(g_stamp), z, sizeof z);
+}
+#endif
+
+// Pass B over slices [bfirst, bend), then (list) the overflow lists of the
+// sweeps this call ran; the last kernel completes `done`.
+hipError_t launch_pass_b(const Launch& L, uint32_t bfirst, uint32_t bend, int sweep, bool list) {
+    const PartitionPlan& pl = L.pl;
+    const PartitionWorkspace& ws = L.ws;
+    uint32_t* dmark = list ? ws.dirty : nullptr;
+    hipEvent_t apply_done = list ? nullptr : L.done;
+    hipError_t e;
+    if (pl.slice_log2 == 21)
+        e = launch_done(k_apply<21>, dim3(2 * (bend - bfirst)), dim3(kApplyBlock), 0u, L.st, apply_done, ws.regions,
+                        ws.counts, pl.grid, pl.cap_segs, pl.nbins, L.gw, L.nw32, bfirst, bend, ws.ovf, dmark, list);
+    else
+        e = launch_done(k_apply<kSliceLog2>, dim3(bend - bfirst), dim3(kApplyBlock), 0u, L.st, apply_done, ws.regions,
+                        ws.counts, pl.grid, pl.cap_segs, pl.nbins, L.gw, L.nw32, bfirst, bend, ws.ovf, dmark, list);
+    if (e != hipSuccess || !list) return e;
+    const uint32_t s0 = sweep >= 0 ? (uint32_t)sweep : 0u, ns = sweep >= 0 ? 1u : pl.sweeps;
+    return launch_done(k_ovf_apply, dim3(ns * pl.grid), dim3(256), 0u, L.st, L.done,
+                       (const uint32_t*)(ws.ovl + (uint64_t)s0 * pl.grid * kOvfListCap),
+                       (const uint32_t*)(ws.ovn + (uint64_t)s0 * pl.grid), (uint32_t)kOvfListCap, L.gw);
+}
+
+// Src: ks::Fixed16 (hashed inline by pass A) or ks::Recs (hash_records first).
+// sweep >= 0: only that sweep's slices — pass A keeps their positions, pass B
+// applies them.
+template <class Src>
+hipError_t launch_partition(const Src& src, const Launch& L, int sweep, bool fresh) {
+    const PartitionPlan& pl = L.pl;
+    const uint32_t bfirst = sweep >= 0 ? (uint32_t)sweep * pl.bins_per_sweep : 0u;
+    const uint32_t bend = sweep >= 0 ? min(pl.nbins, bfirst + pl.bins_per_sweep) : pl.nbins;
+    // Fresh k = 7 builds run the LIST pass A (one key per lane per phase:
+    // the two-key phases of multi-sweep plans overflow ~0.45 % of C5's
+    // positions, which the lists would then OR in serially) and a pass B
+    // that never reads the words; other k zero their word range first and
+    // accumulate.
+    const bool list = fresh && L.k == 7;
+    if (fresh && !list) {
+        const uint64_t wlo = (uint64_t)bfirst << (pl.slice_log2 - 5);
+        const uint64_t whi = min((uint64_t)L.nw32, (uint64_t)bend << (pl.slice_log2 - 5));
+        if (whi > wlo) {
+            const hipError_t e = hipMemsetAsync(L.gw + wlo, 0, (size_t)(whi - wlo) * 4, L.st);
+            if (e != hipSuccess) return e;
+        }
+    }
+    const bool rec = std::is_same<Src, ks::Recs>::value;
+    const WalkKind walk = fits_walk32(L.num_bits)                    ? WalkKind::W32
+                          : !rec && L.num_bits == kMersenneBits      ? WalkKind::Fold
+                                                                     : WalkKind::W64;
+    const BinKernel<Src> kern = pick_k_bin<Src>(L.k, walk, pl.sweeps == 1, pl.keys_per_lane == 2, pl.slice_log2, list);
+    for (uint32_t sw = 0; sw < pl.sweeps; sw++) {
+        if (sweep >= 0 && sw != (uint32_t)sweep) continue;
+        const PassA a = pass_a_args(L, sw);
+        // (k_bin's LDS is static, kLdsBytes; the plan's layout fits it)
+        if ((size_t)(a.nb + 1) * (4 * a.ring + kBinExtraBytes) + kBinJobBytes > kLdsBytes) return hipErrorInvalidValue;
+        kern<<<dim3(pl.grid), dim3(kBinBlock), 0, L.st>>>(src, L.n, L.md, L.k, a);
+        const hipError_t e = hipGetLastError();
+        if (e != hipSuccess) return e;
+    }
+#if LSMB_STAMP
+    report_stamp(L.st);
+#endif
+    L.record_t1();
+    if (bend <= bfirst) return L.record_done();
+    return launch_pass_b(L, bfirst, bend, sweep, list);
+}
+
+// Partition builds of keys pass A does not hash inline (var-len, odd-length,
+// unaligned): hashed first into 12-B walk records in the hash workspace (pass
+// A then walks without the reductions; partition builds have k <= 32).  Pass
+// A's timer (t1) covers this step + k_bin.
+hipError_t hash_records(const KeyBatch& kb, const Launch& L) {
+    const OutRec rec{reinterpret_cast<uint32_t*>(L.ws.hashes), L.md, L.k};
+    if (kb.offsets) return launch_hash(VarLen{kb.data, kb.offsets}, L.n, rec, L.st);
+    return launch_hash(FixedN{kb.data, kb.key_len}, L.n, rec, L.st);
+}
+
+// f(key source of kb)
+template <class F>
+hipError_t with_keys(const KeyBatch& kb, bool aligned16, F&& f) {
+    if (kb.offsets) return f(VarLen{kb.data, kb.offsets});
+    if (aligned16) return f(Fixed16{reinterpret_cast<const uint4*>(kb.data)});
+    return f(FixedN{kb.data, kb.key_len});
+}
+
+}  // namespace
+
+hipError_t launch_build(const KeyBatch& kb, uint32_t num_bits, uint32_t k, uint32_t* gw,
+                        BuildStrategy s, const PartitionWorkspace& ws, int num_cus, hipStream_t st,
+                        BuildTimers* tm, int sweep, bool fresh, hipEvent_t done) {
     const uint32_t nw32 = (uint32_t)(2 * (((uint64_t)num_bits + 63) / 64));
-    if (tm && !t0_done) hipEventRecord(tm->t0, st);
-    constexpr bool kRecSrc = std::is_same<Src, ks::Recs>::value;  // walk records: partition builds only
-    // fresh: the words are output-only.  Single-sweep k = 7 partition builds
-    // write every word in pass B without reading it; the rest start from zeros.
+    Launch L{kb.n, num_bits, k, nw32, Mod32::make(num_bits ? num_bits : 1), gw, ws, num_cus, st, tm, done, {}, {}};
+    if (s == BuildStrategy::None) {
+        if (fresh && num_bits) {
+            const hipError_t e = hipMemsetAsync(gw, 0, (size_t)nw32 * 4, st);  // new(), no inserts
+            if (e != hipSuccess) return e;
+        }
+        return L.record_done();
+    }
+    // every strategy but Partition has one sweep
+    if (sweep > 0 && s != BuildStrategy::Partition) return L.record_done();
+    const bool aligned16 = !kb.offsets && kb.key_len == 16 && (reinterpret_cast<uintptr_t>(kb.data) & 15) == 0;
+    if (s == BuildStrategy::Partition) L.pl = plan_partition(num_bits, k, kb.n, num_cus);
+    if (s == BuildStrategy::Tiled) L.tp = plan_tiled(num_bits, kb.n, num_cus);
+    WorkspaceBytes need = workspace_bytes(s, L.pl, L.tp, num_bits, k, kb.n, aligned16, fresh);
+    if (s == BuildStrategy::Tiled && !ws.hashes) need.hashes = 0;  // optional there: the tiles then hash the keys
+    if (!ws.have.covers(need)) return hipErrorInvalidValue;
+    if (tm) hipEventRecord(tm->t0, st);
+    // fresh: the words are output-only.  Partition builds zero or overwrite
+    // their own word range (launch_partition); the rest start from zeros.
     if (fresh && s != BuildStrategy::Partition) {
         const hipError_t e = hipMemsetAsync(gw, 0, (size_t)nw32 * 4, st);
         if (e != hipSuccess) return e;
     }
-    if (s != BuildStrategy::Partition) {
-      if constexpr (kRecSrc) {
-        return hipErrorInvalidValue;
-      } else if (s == BuildStrategy::Lds) {
-        const size_t smem = (size_t)nw32 * 4;
-        // ~8 Ki keys per workgroup keeps the final per-word OR cheap.
-        uint64_t g = (n + 8191) / 8192;
-        const uint64_t gmax = (uint64_t)num_cus * (smem <= 40 * 1024 ? 4 : 1);
-        if (g > gmax) g = gmax;
-        if (g < 1) g = 1;
-        set_max_lds((const void*)k_build_lds<Src>);
-        k_build_lds<Src><<<dim3((uint32_t)g), dim3(1024), smem, st>>>(src, n, md, k, nw32, gw);
-        if (tm) hipEventRecord(tm->t1, st);
-    } else if (s == BuildStrategy::Tiled) {
-        const TiledPlan tp = plan_tiled(num_bits, n, num_cus);
-        if (!ws.regions || tp.scratch_bytes > ws.region_bytes) return hipErrorInvalidValue;
-        uint32_t* tiles = reinterpret_cast<uint32_t*>(ws.regions);
-        if (ws.hashes && ws.hash_bytes >= n * 16 && !std::is_same<Src, Hashed>::value) {
-            // every slice's workgroups re-read the keys: hash them once into
-            // 16-B records (L2/MALL-resident at these sizes) and tile over those
-            const uint64_t g = (n + 255) / 256;
-            if (g > 0x7FFFFFFFull) return hipErrorInvalidValue;
-            if constexpr (std::is_same<Src, VarLen>::value)
-                launch_hash_var(src, n, OutH128(ws.hashes), st);
-            else
-                k_hash<Src, OutH128><<<dim3((uint32_t)g), dim3(256), 0, st>>>(src, n, OutH128(ws.hashes));
-            const Hashed hs{ws.hashes};
-            set_max_lds((const void*)k_build_tiled<Hashed>);
-            k_build_tiled<Hashed><<<dim3(tp.chunks * tp.nslices), dim3(1024), kSliceWords32 * 4, st>>>(
-                hs, n, md, k, tp.nslices, nw32, tp.stride32, tiles);
-        } else {
-            set_max_lds((const void*)k_build_tiled<Src>);
-            k_build_tiled<Src><<<dim3(tp.chunks * tp.nslices), dim3(1024), kSliceWords32 * 4, st>>>(
-                src, n, md, k, tp.nslices, nw32, tp.stride32, tiles);
-        }
-        if (tm) hipEventRecord(tm->t1, st);
-        hipError_t e = launch_or_reduce(gw, tiles, nw32, tp.chunks, tp.stride32, st, done);
-        if (e != hipSuccess) return e;
-        done_set = done != nullptr;
-    } else if (s == BuildStrategy::Atomic) {
-        uint64_t g = (n + 255) / 256;
-        if (g > (uint64_t)num_cus * 8) g = (uint64_t)num_cus * 8;
-        k_build_atomic<Src><<<dim3((uint32_t)g), dim3(256), 0, st>>>(src, n, md, k, gw);
-        if (tm) hipEventRecord(tm->t1, st);
-      }
-    } else if constexpr (Src::kPrehash) {
-        // hashed first, into 12-B walk records (pass A then walks without
-        // the reductions; partition builds have k <= 32)
-        if (ws.hash_bytes < n * 12) return hipErrorInvalidValue;
-        const uint64_t g = (n + 255) / 256;
-        if (g > 0x7FFFFFFFull) return hipErrorInvalidValue;
-        const OutRec rec{reinterpret_cast<uint32_t*>(ws.hashes), md, k};
-        if constexpr (std::is_same<Src, VarLen>::value)
-            launch_hash_var(src, n, rec, st);
-        else
-            k_hash<Src, OutRec><<<dim3((uint32_t)g), dim3(256), 0, st>>>(src, n, rec);
-        // pass A's timer (t1) covers k_hash + k_bin
-        return build_with(ks::Recs{reinterpret_cast<const uint32_t*>(ws.hashes)}, n, num_bits, k, gw, s, ws, num_cus,
-                          st, tm, sweep, fresh, /*t0_done=*/true, done);
-    } else {
-        const PartitionPlan pl = plan_partition(num_bits, k, n, num_cus);
-        if (pl.region_bytes > ws.region_bytes || pl.counts_bytes > ws.counts_bytes) return hipErrorInvalidValue;
-        const uint32_t bfirst = sweep >= 0 ? (uint32_t)sweep * pl.bins_per_sweep : 0u;
-        const uint32_t bend = sweep >= 0 ? min(pl.nbins, bfirst + pl.bins_per_sweep) : pl.nbins;
-        // Fresh k = 7 builds run the LIST pass A (one key per lane per phase:
-        // the two-key phases of multi-sweep plans overflow ~0.45 % of C5's
-        // positions, which the lists would then OR in serially) and a pass B
-        // that never reads the words; other k zero their word range first and
-        // accumulate.
-        const bool list = fresh && k == 7;
-        if (list && (!ws.ovf || !ws.dirty || ws.ovf_units * kSliceWords32 < nw32 || !ws.ovl ||
-                     ws.ovl_groups < pl.grid * pl.sweeps))
-            return hipErrorInvalidValue;
-        if (fresh && !list) {
-            const uint64_t wlo = (uint64_t)bfirst << (pl.slice_log2 - 5);
-            const uint64_t whi = min((uint64_t)nw32, (uint64_t)bend << (pl.slice_log2 - 5));
-            if (whi > wlo) {
-                const hipError_t e = hipMemsetAsync(gw + wlo, 0, (size_t)(whi - wlo) * 4, st);
-                if (e != hipSuccess) return e;
-            }
-        }
-        const bool w32 = fits_walk32(num_bits);
-        // walks: from (h1, h2), or replayed from 12-B records
-        constexpr bool kRec = std::is_same<Src, ks::Recs>::value;
-        using Walk32 = std::conditional_t<kRec, RecWalk32, lsmb::Walk32>;
-        using Walk64 = std::conditional_t<kRec, RecWalk64, lsmb::Walk64>;
-        for (uint32_t sw = 0; sw < pl.sweeps; sw++) {
-            if (sweep >= 0 && sw != (uint32_t)sweep) continue;
-            PassA a;
-            a.b0 = sw * pl.bins_per_sweep;
-            a.nb = min(pl.bins_per_sweep, pl.nbins - a.b0);
-            a.grid = pl.grid;
-            a.cap = pl.cap_segs;
-            a.ring = pl.ring;
-            a.regions = ws.regions;
-            a.counts = ws.counts;
-            a.gw = gw;
-            a.ovf = ws.ovf;
-            a.dirty = ws.dirty;
-            a.ovl = ws.ovl + (uint64_t)sw * pl.grid * kOvfListCap;  // one list per workgroup per sweep
-            a.ovn = ws.ovn + (uint64_t)sw * pl.grid;
-            a.ovl_cap = kOvfListCap;
-            a.err = ws.err;
-            a.nbins = pl.nbins;
-            // (k_bin's LDS is static, kLdsBytes; the plan's layout fits it)
-            if ((size_t)(a.nb + 1) * (4 * a.ring + kBinExtraBytes) + kBinJobBytes > kLdsBytes) return hipErrorInvalidValue;
-            auto go = [&](auto kern) { kern<<<dim3(pl.grid), dim3(kBinBlock), 0, st>>>(src, n, md, k, a); };
-            const bool full = pl.sweeps == 1;
-            auto go7 = [&](auto slc) {  // k = 7 (BloomFilter::new at fpr 0.01), bin width 2^SL
-                constexpr int SL = decltype(slc)::value;
-                const bool two = pl.keys_per_lane == 2;
-                auto pick = [&](auto wtag) {
-                    using W = typename decltype(wtag)::type;
-                    if (list) {
-                        if (full) go(k_bin<Src, W, 7, true, true, 1, SL, true>);
-                        else go(k_bin<Src, W, 7, true, false, 1, SL, true>);
-                    } else {
-                        if (full && two) go(k_bin<Src, W, 7, true, true, 2, SL>);
-                        else if (full) go(k_bin<Src, W, 7, true, true, 1, SL>);
-                        else if (two) go(k_bin<Src, W, 7, true, false, 2, SL>);
-                        else go(k_bin<Src, W, 7, true, false, 1, SL>);
-                    }
-                };
-                if (w32) {
-                    pick(WalkTag<Walk32>{});
-                } else if constexpr (!kRec) {
-                    // the saturated u32 filter (C5): folds instead of reductions
-                    if (num_bits == kMersenneBits) pick(WalkTag<WalkM>{});
-                    else pick(WalkTag<Walk64>{});
-                } else {
-                    pick(WalkTag<Walk64>{});
-                }
-            };
-            if (k == 7) {
-                if (pl.slice_log2 == 21) go7(std::integral_constant<int, 21>{});
-                else go7(std::integral_constant<int, kSliceLog2>{});
-            } else if (k <= 8) {
-                if (w32) go(k_bin<Src, Walk32, 8, false, false>); else go(k_bin<Src, Walk64, 8, false, false>);
-            } else if (k <= 16) {
-                if (w32) go(k_bin<Src, Walk32, 16, false, false>); else go(k_bin<Src, Walk64, 16, false, false>);
+    hipError_t e;
+    switch (s) {
+        case BuildStrategy::Lds: e = with_keys(kb, aligned16, [&](auto src) { return launch_lds(src, L); }); break;
+        case BuildStrategy::Tiled: e = with_keys(kb, aligned16, [&](auto src) { return launch_tiled(src, L); }); break;
+        case BuildStrategy::Atomic: e = with_keys(kb, aligned16, [&](auto src) { return launch_atomic(src, L); }); break;
+        default:  // Partition
+            if (aligned16) {
+                e = launch_partition(Fixed16{reinterpret_cast<const uint4*>(kb.data)}, L, sweep, fresh);
             } else {
-                if (w32) go(k_bin<Src, Walk32, 32, false, false>); else go(k_bin<Src, Walk64, 32, false, false>);
+                e = hash_records(kb, L);
+                if (e == hipSuccess)
+                    e = launch_partition(ks::Recs{reinterpret_cast<const uint32_t*>(ws.hashes)}, L, sweep, fresh);
             }
-            hipError_t e = hipGetLastError();
-            if (e != hipSuccess) return e;
-        }
-#if LSMB_STAMP
-        {
-            unsigned long long h[8];
-            hipStreamSynchronize(st);
-            hipMemcpyFromSymbol(h, HIP_SYMBOL(g_stamp), sizeof h);
-            const double ph = (double)h[4] ? (double)h[4] : 1.0;  // wave-phases
-            const double tot = (double)(h[0] + h[1] + h[2] + h[3]);
-            fprintf(stderr, "[stamp] waves %llu phases/wave %.1f cycles/phase %.0f: work %.0f (%.1f%%) b1 %.0f (%.1f%%) "
-                            "flush %.0f (%.1f%%) b2 %.0f (%.1f%%)\n",
-                    h[5], ph / (double)h[5], tot / ph, h[0] / ph, 100 * h[0] / tot, h[1] / ph, 100 * h[1] / tot,
-                    h[2] / ph, 100 * h[2] / tot, h[3] / ph, 100 * h[3] / tot);
-            const unsigned long long z[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-            hipMemcpyToSymbol(HIP_SYMBOL(g_stamp), z, sizeof z);
-        }
-#endif
-        if (tm) hipEventRecord(tm->t1, st);
-        if (bend > bfirst) {
-            uint32_t* dmark = list ? ws.dirty : nullptr;
-            hipEvent_t apply_done = list ? nullptr : done;  // (the last kernel completes `done`)
-            hipError_t e;
-            if (pl.slice_log2 == 21)
-                e = launch_done(k_apply<21>, dim3(2 * (bend - bfirst)), dim3(kApplyBlock), 0u, st, apply_done, ws.regions,
-                                ws.counts, pl.grid, pl.cap_segs, pl.nbins, gw, nw32, bfirst, bend, ws.ovf, dmark, list);
-            else
-                e = launch_done(k_apply<kSliceLog2>, dim3(bend - bfirst), dim3(kApplyBlock), 0u, st, apply_done, ws.regions,
-                                ws.counts, pl.grid, pl.cap_segs, pl.nbins, gw, nw32, bfirst, bend, ws.ovf, dmark, list);
-            if (e != hipSuccess) return e;
-            if (list) {  // the lists of the sweeps this call ran
-                const uint32_t s0 = sweep >= 0 ? (uint32_t)sweep : 0u, ns = sweep >= 0 ? 1u : pl.sweeps;
-                e = launch_done(k_ovf_apply, dim3(ns * pl.grid), dim3(256), 0u, st, done,
-                                (const uint32_t*)(ws.ovl + (uint64_t)s0 * pl.grid * kOvfListCap),
-                                (const uint32_t*)(ws.ovn + (uint64_t)s0 * pl.grid), (uint32_t)kOvfListCap, gw);
-                if (e != hipSuccess) return e;
-            }
-            done_set = done != nullptr;
-        }
     }
-    if (done && !done_set) hipEventRecord(done, st);
+    if (e != hipSuccess) return e;
     if (tm) {
         hipEventRecord(tm->t2, st);
         tm->valid = true;
     }
     return hipGetLastError();
-}
-
-}  // namespace
-
-const char* strategy_name(BuildStrategy s) {
-    switch (s) {
-        case BuildStrategy::None: return "none";
-        case BuildStrategy::Lds: return "lds";
-        case BuildStrategy::Partition: return "partition";
-        case BuildStrategy::Atomic: return "atomic";
-        case BuildStrategy::Tiled: return "tiled";
-    }
-    return "?";
-}
-
-BuildStrategy pick_build_strategy(uint32_t num_bits, uint32_t k, uint64_t n) {
-    if (n == 0 || k == 0 || num_bits == 0) return BuildStrategy::None;
-    const uint64_t nw32 = 2 * (((uint64_t)num_bits + 63) / 64);
-    if (nw32 <= kLdsFilterMaxWords32) return BuildStrategy::Lds;
-    if (k > 32) return BuildStrategy::Atomic;
-    // Few keys into a big filter: scattered atomics beat a full-slice RMW.
-    if (n * (uint64_t)k < nw32 / 16) return BuildStrategy::Atomic;
-    // Fewer than 64 slices (< 8 MiB filters): too few LDS buffers to spread
-    // a workgroup's claims; memory-side atomics on the small filter instead.
-    if (nw32 <= (uint64_t)kTiledMaxSlices * kSliceWords32 && k <= 32) return BuildStrategy::Tiled;
-    if (nw32 < 64ull * kSliceWords32) return BuildStrategy::Atomic;
-    return BuildStrategy::Partition;
-}
-
-namespace {
-PartitionPlan plan_partition_sl(uint32_t num_bits, uint32_t k, uint64_t n, int num_cus, uint32_t sl) {
-    PartitionPlan pl;
-    pl.slice_log2 = sl;
-    pl.nbins = (uint32_t)(((uint64_t)num_bits + (1ull << sl) - 1) >> sl);
-    // Entries a slice's ring receives per pass A phase (1024 keys), and the
-    // ring that holds a segment's worth of leftovers plus a phase's arrivals
-    // with margin.  Claims past the ring fall back to exact global atomics.
-    const double lambda = (double)kBinBlock * k * fmin(1.0, (double)(1u << sl) / (double)num_bits);
-    uint32_t need = kSegEntries + (uint32_t)ceil(lambda + 2.0 * sqrt(lambda));
-    need = (need + 7) & ~7u;
-    if (need > kMaxRing) need = kMaxRing;
-    // Fewest sweeps whose slices fit LDS with that ring; each sweep re-reads
-    // and re-hashes the keys and keeps only its own slices' positions.
-    pl.sweeps = (pl.nbins + kMaxBinsPerSweep - 1) / kMaxBinsPerSweep;
-    for (;; pl.sweeps++) {
-        pl.bins_per_sweep = (pl.nbins + pl.sweeps - 1) / pl.sweeps;
-        uint32_t r = (kBinLdsBudget / (pl.bins_per_sweep + 1) - kBinExtraBytes) / 4;  // + the sink slice
-        r &= ~7u;
-        if (r > kMaxRing) r = kMaxRing;
-        if (r >= need || pl.bins_per_sweep == 1) {
-            pl.ring = r;
-            break;
-        }
-    }
-    // k = 7 sweeps take two keys per lane per phase when the ring holds a
-    // phase's doubled arrivals to within one 8-entry group: C5's 32-entry
-    // rings (2^21-bit bins, 1024 per sweep; need2 = 40) then send ~0.45 % of
-    // the positions to the exact global-atomic path, and pass A still gains
-    // (C5 shard: 2.38 -> 2.33 ms).  Single-sweep filters keep one even where
-    // the rings would hold two: it is slower there (4.97e8 bits, 100 M keys:
-    // 0.995 -> 1.026 ms).  LSMB_SWEEP_PER=1 / =2 forces one / two
-    // (measurement knob).
-    if (k == 7) {
-        const char* e = getenv("LSMB_SWEEP_PER");
-        const uint32_t need2 = (kSegEntries + (uint32_t)ceil(2 * lambda + 2.0 * sqrt(2 * lambda)) + 7) & ~7u;
-        // Not for the saturated 2^32-1-bit filter: with its fold walk (WalkM)
-        // the doubled phase is slower (C5 shard, accumulate: pass A 2.074 ->
-        // 2.136 ms; tools/r04_c5per.sh).
-        const bool auto2 = pl.sweeps > 1 && pl.ring + 8 >= need2 && num_bits != kMersenneBits;
-        if ((auto2 && !(e && atoi(e) == 1)) || (e && atoi(e) == 2)) pl.keys_per_lane = 2;
-    }
-    // 1024-thread workgroups (one resident per CU), at least ~kBinBlock keys
-    // each: two per CU for 2^20-bit bins — pass B then streams twice as many,
-    // half-size regions per slice (C2: pass B 0.448 -> 0.411 ms, pass A
-    // unchanged) — one for 2^21-bit bins, whose two half-bin workgroups each
-    // read every region (C5 shard: pass B 0.843 -> 0.986 ms at two).
-    // LSMB_BIN_WGS_PER_CU overrides (measurement knob, tools/bin_wgs.sh).
-    const uint64_t gmax = (n + kBinBlock - 1) / kBinBlock;
-    static const long wenv = [] {
-        const char* e = getenv("LSMB_BIN_WGS_PER_CU");
-        return e ? atol(e) : 0L;
-    }();
-    const uint64_t wpc = wenv >= 1 && wenv <= 4 ? (uint64_t)wenv : (sl == kSliceLog2 ? 2 : 1);
-    uint64_t g = (uint64_t)num_cus * wpc;
-    if (g > gmax) g = gmax;
-    if (g < 1) g = 1;
-    pl.grid = (uint32_t)g;
-    const uint64_t keys_w = (n + g - 1) / g;  // workgroup w hashes keys [w*keys_w, (w+1)*keys_w)
-    double p = (double)(1u << sl) / (double)num_bits;
-    if (p > 1.0) p = 1.0;
-    const double mu = (double)keys_w * k * p;
-    const double cap_e = mu + 8.0 * sqrt(mu) + 2.0 * kSegEntries;
-    pl.cap_segs = (uint32_t)ceil(cap_e / kSegEntries);
-    // A region holds at most kMaxRegionSegs segments
-    // a bigger plan is reported as unbounded so callers chunk the keys.
-    // (and a workgroup's regions within pass A's 2^31-byte buffer range)
-    const bool fits = pl.cap_segs <= kMaxRegionSegs && (uint64_t)pl.nbins * pl.cap_segs * kSegSlotBytes < (1ull << 31);
-    pl.region_bytes = fits ? (uint64_t)pl.nbins * pl.grid * pl.cap_segs * kSegSlotBytes : ~0ull >> 2;
-    pl.counts_bytes = (uint64_t)pl.nbins * pl.grid * 4;
-    return pl;
-}
-}  // namespace
-
-// Bins of 2^20 bits (one pass B workgroup's LDS) unless the filter needs
-// several sweeps: then 2^21-bit bins halve the sweeps (each re-reads and
-// re-hashes every key) for a second read of each bin's regions in pass B.
-// k = 7 only (the kernels instantiated for it); LSMB_SLICE_LOG2=20 pins 2^20,
-// =21 forces 2^21 (measurement knobs).
-PartitionPlan plan_partition(uint32_t num_bits, uint32_t k, uint64_t n, int num_cus) {
-    const PartitionPlan p20 = plan_partition_sl(num_bits, k, n, num_cus, kSliceLog2);
-    const char* e = getenv("LSMB_SLICE_LOG2");
-    if (k == 7 && e && atoi(e) == 21 && num_bits > (1u << 21))  // measurement: force 2^21-bit bins
-        return plan_partition_sl(num_bits, k, n, num_cus, 21);
-    if (p20.sweeps < 2 || k != 7) return p20;
-    if (e && atoi(e) == 20) return p20;
-    const PartitionPlan p21 = plan_partition_sl(num_bits, k, n, num_cus, 21);
-    return p21.sweeps < p20.sweeps ? p21 : p20;
-}
-
-TiledPlan plan_tiled(uint32_t num_bits, uint64_t n, int num_cus) {
-    TiledPlan tp;
-    const uint64_t nw32 = 2 * (((uint64_t)num_bits + 63) / 64);
-    tp.nslices = (uint32_t)((nw32 + kSliceWords32 - 1) / kSliceWords32);
-    // ~2 workgroups per CU in all, at least 4 Ki keys per chunk
-    uint64_t ch = (2ull * (uint64_t)num_cus + tp.nslices - 1) / tp.nslices;
-    const uint64_t by_keys = (n + 4095) / 4096;
-    if (ch > by_keys) ch = by_keys;
-    if (ch < 1) ch = 1;
-    tp.chunks = (uint32_t)ch;
-    tp.stride32 = (uint64_t)tp.nslices * kSliceWords32;
-    tp.scratch_bytes = (uint64_t)tp.chunks * tp.stride32 * 4;
-    return tp;
-}
-
-uint64_t partition_chunk_keys(uint32_t num_bits, uint32_t k, uint64_t max_bytes, int num_cus) {
-    uint64_t lo = 0, hi = (1ull << 40);
-    while (lo + 1 < hi) {  // largest n whose plan fits
-        const uint64_t mid = lo + (hi - lo) / 2;
-        const PartitionPlan pl = plan_partition(num_bits, k, mid, num_cus);
-        if (pl.region_bytes + pl.counts_bytes <= max_bytes) lo = mid; else hi = mid;
-    }
-    return lo;
-}
-
-hipError_t launch_build(const KeyBatch& kb, uint32_t num_bits, uint32_t k, uint32_t* gw,
-                        BuildStrategy s, const PartitionWorkspace& ws, int num_cus, hipStream_t st,
-                        BuildTimers* tm, int sweep, bool fresh, hipEvent_t done) {
-    if (s == BuildStrategy::None) {
-        if (fresh && num_bits) {
-            const hipError_t e = hipMemsetAsync(gw, 0, (size_t)(((uint64_t)num_bits + 63) / 64) * 8, st);  // new(), no inserts
-            if (e != hipSuccess) return e;
-        }
-        return done ? hipEventRecord(done, st) : hipSuccess;
-    }
-    if (kb.offsets)
-        return build_with(VarLen{kb.data, kb.offsets}, kb.n, num_bits, k, gw, s, ws, num_cus, st, tm, sweep, fresh, false, done);
-    if (kb.key_len == 16 && (reinterpret_cast<uintptr_t>(kb.data) & 15) == 0)
-        return build_with(Fixed16{reinterpret_cast<const uint4*>(kb.data)}, kb.n, num_bits, k, gw, s, ws,
-                          num_cus, st, tm, sweep, fresh, false, done);
-    return build_with(FixedN{kb.data, kb.key_len}, kb.n, num_bits, k, gw, s, ws, num_cus, st, tm, sweep, fresh, false, done);
 }
 
 hipError_t launch_or_reduce(uint32_t* dst, const uint32_t* src, uint64_t nw32, uint32_t nsrc,

@@ -2,7 +2,8 @@
 //
 // Host-side plumbing only: argument validation with the reference's error
 // behaviour, the per-GPU context (stream, events, grow-only device arenas),
-// chunking of large builds, and the format functions of src/bloom/mod.rs.
+// the format functions of src/bloom/mod.rs, the probe and the filter set.
+// The builds themselves are orchestrated in build_dev.hip.
 #include <math.h>
 #include <stdarg.h>
 #include <stdio.h>
@@ -55,11 +56,12 @@ uint32_t rd32le(const uint8_t* p) {
     return (uint32_t)p[0] | ((uint32_t)p[1] << 8) | ((uint32_t)p[2] << 16) | ((uint32_t)p[3] << 24);
 }
 
-uint64_t workspace_limit_bytes() {
-    const char* s = getenv("LSMB_WORKSPACE_MB");
-    uint64_t mb = s ? strtoull(s, nullptr, 10) : 8192;
-    if (mb < 16) mb = 16;
-    return mb << 20;
+// The 12-byte header of BloomFilter::serialize (src/bloom/mod.rs:102-115):
+// num_hashes, num_bits, num_u64s as little-endian u32.
+void write_header(uint8_t* out, uint32_t num_bits, uint32_t k) {
+    const uint32_t hdr[3] = {k, num_bits, (uint32_t)nwords64(num_bits)};
+    for (int j = 0; j < 3; j++)
+        for (int b = 0; b < 4; b++) out[4 * j + b] = (uint8_t)(hdr[j] >> (8 * b));
 }
 }  // namespace
 
@@ -94,119 +96,6 @@ void report_stats(lsmb_ctx* c) {
 #endif
 }
 
-namespace {
-int build_dev_ws(lsmb_ctx* c, const KeyBatch& kb_all, uint32_t num_bits, uint32_t k, uint32_t* dw, hipStream_t st,
-                 BuildStrategy s, int sweep, bool fresh, hipEvent_t done = nullptr);
-}  // namespace
-
-// Device build of one batch, chunked so the partition workspace stays bounded.
-int build_dev(lsmb_ctx* c, const KeyBatch& kb_all, uint32_t num_bits, uint32_t k, uint32_t* dw,
-              hipStream_t st, int sweep, bool fresh) {
-    BuildStrategy s = pick_build_strategy(num_bits, k, kb_all.n);
-    // LSMB_FORCE_STRATEGY=atomic: measurement override;
-    // the filter is the same either way.
-    if (const char* f = getenv("LSMB_FORCE_STRATEGY"))
-        if ((s == BuildStrategy::Partition || s == BuildStrategy::Tiled) && !strcmp(f, "atomic")) s = BuildStrategy::Atomic;
-    c->tm.valid = false;
-    if (s == BuildStrategy::None) {  // fresh: new() with no inserts, all-zero words
-        if (fresh && num_bits) HIP_TRY(hipMemsetAsync(dw, 0, nwords64(num_bits) * 8, st));
-        return LSMB_OK;
-    }
-    if (s != BuildStrategy::Tiled && s != BuildStrategy::Partition)
-        return build_dev_ws(c, kb_all, num_bits, k, dw, st, s, sweep, fresh);
-    // Tiled and partition builds use the context's shared workspace: a build
-    // issued on a different stream than the last one waits for it (two
-    // streams' builds would otherwise overwrite each other's regions).  On the
-    // same stream, stream order already serialises them: no wait packet (a
-    // barrier packet between consecutive builds costs the stream ~10 us).
-    // ws_done is completed by the build's last kernel itself (launch_done): a
-    // separate event record would put a marker packet, ~6 us, between
-    // back-to-back builds.
-    if (c->ws_stream && c->ws_stream != st) HIP_TRY(hipStreamWaitEvent(st, c->ws_done, 0));
-    const int rc = build_dev_ws(c, kb_all, num_bits, k, dw, st, s, sweep, fresh, c->ws_done);
-    if (rc != LSMB_OK) HIP_TRY(hipEventRecord(c->ws_done, st));  // (a failed build may have launched nothing)
-    c->ws_stream = st;
-    return rc;
-}
-
-namespace {
-int build_dev_ws(lsmb_ctx* c, const KeyBatch& kb_all, uint32_t num_bits, uint32_t k, uint32_t* dw, hipStream_t st,
-                 BuildStrategy s, int sweep, bool fresh, hipEvent_t done) {
-    if (s == BuildStrategy::Tiled) {
-        const TiledPlan tp = plan_tiled(num_bits, kb_all.n, c->num_cus);
-        HIP_TRY(c->ws_regions.ensure(tp.scratch_bytes));
-        PartitionWorkspace ws;
-        ws.regions = (uint64_t*)c->ws_regions.p;
-        ws.region_bytes = c->ws_regions.bytes;
-        if (!getenv("LSMB_TILED_NO_PREHASH")) {  // measurement switch
-            HIP_TRY(c->ws_hashes.ensure(kb_all.n * 16));
-            ws.hashes = (uint4*)c->ws_hashes.p;
-            ws.hash_bytes = c->ws_hashes.bytes;
-        }
-        HIP_TRY(launch_build(kb_all, num_bits, k, dw, s, ws, c->num_cus, st, c->timing ? &c->tm : nullptr, sweep,
-                             fresh, done));
-        return LSMB_OK;
-    }
-    if (s != BuildStrategy::Partition) {
-        HIP_TRY(launch_build(kb_all, num_bits, k, dw, s, PartitionWorkspace{}, c->num_cus, st,
-                             c->timing ? &c->tm : nullptr, sweep, fresh, done));
-        return LSMB_OK;
-    }
-    uint64_t chunk = partition_chunk_keys(num_bits, k, workspace_limit_bytes(), c->num_cus);
-    if (chunk == 0) return fail(LSMB_ENOMEM, "partition workspace limit too small");
-    chunk = std::min(chunk, kb_all.n);
-    const PartitionPlan pl = plan_partition(num_bits, k, chunk, c->num_cus);
-    HIP_TRY(c->ws_regions.ensure(pl.region_bytes));
-    HIP_TRY(c->ws_counts.ensure(pl.counts_bytes));
-    PartitionWorkspace ws;
-    ws.regions = (uint64_t*)c->ws_regions.p;
-    ws.counts = (uint32_t*)c->ws_counts.p;
-    ws.err = (uint32_t*)c->err.p;
-    ws.region_bytes = c->ws_regions.bytes;
-    ws.counts_bytes = c->ws_counts.bytes;
-    if (fresh && k == 7) {
-        // a fresh k = 7 build (the LIST pass A, bloom_build.hip): the overflow
-        // lists (per workgroup per sweep), and the overflow words + unit marks
-        // of the whole filter for lists that fill up, zeroed once when
-        // (re)allocated
-        const uint64_t units = ((nwords64(num_bits) * 2) + kSliceWords32 - 1) / kSliceWords32;
-        // each buffer is zeroed right after it is (re)allocated, before the
-        // next allocation can fail: a grown buffer never stays unzeroed
-        const size_t ob = c->ws_ovf.bytes, db = c->ws_dirty.bytes;
-        HIP_TRY(c->ws_ovf.ensure(units * kSliceWords32 * 4));
-        if (c->ws_ovf.bytes != ob) HIP_TRY(hipMemsetAsync(c->ws_ovf.p, 0, c->ws_ovf.bytes, st));
-        HIP_TRY(c->ws_dirty.ensure(units * 4));
-        if (c->ws_dirty.bytes != db) HIP_TRY(hipMemsetAsync(c->ws_dirty.p, 0, c->ws_dirty.bytes, st));
-        ws.ovf = (uint32_t*)c->ws_ovf.p;
-        ws.dirty = (uint32_t*)c->ws_dirty.p;
-        ws.ovf_units = std::min<uint64_t>(c->ws_ovf.bytes / (kSliceWords32 * 4), c->ws_dirty.bytes / 4);
-        HIP_TRY(c->ws_ovl.ensure((uint64_t)pl.grid * pl.sweeps * kOvfListCap * 4));
-        HIP_TRY(c->ws_ovn.ensure((uint64_t)pl.grid * pl.sweeps * 4));
-        ws.ovl = (uint32_t*)c->ws_ovl.p;
-        ws.ovn = (uint32_t*)c->ws_ovn.p;
-        ws.ovl_groups = (uint32_t)std::min<uint64_t>(c->ws_ovn.bytes / 4, c->ws_ovl.bytes / (kOvfListCap * 4ull));
-    }
-    const bool fixed16 = !kb_all.offsets && kb_all.key_len == 16 && (reinterpret_cast<uintptr_t>(kb_all.data) & 15) == 0;
-    if (!fixed16) {  // pre-hashed pass A (ks::Hashed): 16 B per key of the chunk
-        HIP_TRY(c->ws_hashes.ensure(chunk * 16));
-        ws.hashes = (uint4*)c->ws_hashes.p;
-        ws.hash_bytes = c->ws_hashes.bytes;
-    }
-    for (uint64_t first = 0; first < kb_all.n; first += chunk) {
-        KeyBatch kb = kb_all;
-        kb.n = std::min(chunk, kb_all.n - first);
-        if (kb.offsets)
-            kb.offsets += first;  // VarLen offsets are absolute into data
-        else
-            kb.data += first * kb.key_len;
-        // fresh: the first chunk writes every word of the range, the rest accumulate
-        HIP_TRY(launch_build(kb, num_bits, k, dw, s, ws, c->num_cus, st, c->timing ? &c->tm : nullptr, sweep,
-                             fresh && first == 0, done));  // (each chunk's last kernel re-arms `done`)
-    }
-    return LSMB_OK;
-}
-}  // namespace
-
 // Host single-key walks (the same arithmetic the kernels run).
 template <class W, class F>
 void walk_key(const uint8_t* key, uint64_t len, uint32_t num_bits, uint32_t k, F&& f) {
@@ -237,154 +126,6 @@ int check_offsets(const uint64_t* offsets, uint64_t n) {
     return LSMB_OK;
 }
 
-uint64_t h2d_chunk_bytes() {
-    const char* s = getenv("LSMB_H2D_CHUNK_MB");
-    uint64_t mb = s ? strtoull(s, nullptr, 10) : 128;
-    if (mb < 1) mb = 1;
-    return mb << 20;
-}
-
-// Build from keys in host memory (the flush / compaction path: keys come from a
-// memtable or merge iterator, src/db/mod.rs:379-383).  The keys go up in chunks
-// of <= h2d_chunk_bytes() through two device staging slots: chunk i+1's H2D on
-// the copy stream overlaps chunk i's kernels on the build stream, so the build
-// hides under the PCIe transfer.  words_in == NULL starts from a zeroed filter
-// (BloomFilter::new), else from those words (OR-accumulate); the finished words
-// are copied to words_out (host, any alignment: lsmb_build_block points it at
-// the serialized block body).  Synchronous.
-// Small host builds (an SST flush of a few thousand keys): one pinned staging
-// buffer, plain memcpys into and out of it and true async DMA on the build
-// stream — pageable copies would each stage synchronously — and no copy
-// stream.  Latency, not bandwidth, is what these calls pay.
-constexpr uint64_t kSmallHostBuild = 1ull << 20;  // bytes of keys + offsets + words
-
-int host_build_small(lsmb_ctx* c, const uint8_t* data, const uint64_t* offsets, uint32_t key_len, uint64_t n,
-                     uint32_t num_bits, uint32_t k, const uint64_t* words_in, uint8_t* words_out) {
-    const uint64_t nw = nwords64(num_bits);
-    const uint64_t base = offsets ? offsets[0] : 0;
-    const uint64_t kbytes = offsets ? offsets[n] - base : n * (uint64_t)key_len;
-    const uint64_t obytes = offsets ? (n + 1) * 8 : 0;
-    const uint64_t kpad = (kbytes + 15) & ~15ull, opad = (obytes + 15) & ~15ull;
-    const uint64_t need = kpad + opad + nw * 8 + 64;
-    if (c->pin_small_cap < need) {
-        c->pinned_retired.retire(c->pin_small);  // a D2H of an earlier call may not have left it
-        c->pin_small = nullptr;
-        c->pin_small_cap = 0;
-        const uint64_t cap = std::max<uint64_t>(need, kSmallHostBuild + 64);
-        if (hipHostMalloc((void**)&c->pin_small, cap, 0) != hipSuccess)
-            return fail(LSMB_ENOMEM, "pinned staging (%llu B)", (unsigned long long)cap);
-        c->pin_small_cap = cap;
-    }
-    uint8_t* pk = c->pin_small;
-    uint64_t* po = (uint64_t*)(c->pin_small + kpad);
-    uint64_t* pw = (uint64_t*)(c->pin_small + kpad + opad);
-    HIP_TRY(c->words.ensure(nw * 8));
-    HIP_TRY(c->kslot[0].ensure(kpad + 16));
-    uint32_t* dw = (uint32_t*)c->words.p;
-    // the previous small build's D2H out of this buffer has completed (synchronous calls)
-    if (kbytes) memcpy(pk, data + base, kbytes);
-    if (kbytes) HIP_TRY(hipMemcpyAsync(c->kslot[0].p, pk, kbytes, hipMemcpyHostToDevice, c->st));
-    if (offsets) {
-        for (uint64_t j = 0; j <= n; j++) po[j] = offsets[j] - base;
-        HIP_TRY(c->oslot[0].ensure(obytes));
-        HIP_TRY(hipMemcpyAsync(c->oslot[0].p, po, obytes, hipMemcpyHostToDevice, c->st));
-    }
-    if (words_in) {
-        memcpy(pw, words_in, nw * 8);
-        HIP_TRY(hipMemcpyAsync(dw, pw, nw * 8, hipMemcpyHostToDevice, c->st));
-    } else {
-        HIP_TRY(hipMemsetAsync(dw, 0, nw * 8, c->st));
-    }
-    KeyBatch kb{(const uint8_t*)c->kslot[0].p, offsets ? (const uint64_t*)c->oslot[0].p : nullptr, key_len,
-                (!offsets && key_len == 0) ? 1 : n};
-    if (int rc = build_dev(c, kb, num_bits, k, dw, c->st)) return rc;
-    HIP_TRY(hipMemcpyAsync(pw, dw, nw * 8, hipMemcpyDeviceToHost, c->st));
-    HIP_TRY(hipStreamSynchronize(c->st));
-    memcpy(words_out, pw, nw * 8);
-    return LSMB_OK;
-}
-
-int host_build_dev(lsmb_ctx* c, const uint8_t* data, const uint64_t* offsets, uint32_t key_len, uint64_t n,
-                   uint32_t num_bits, uint32_t k, uint32_t* dw) {
-    if (!offsets && key_len == 0) {
-        // every key is the empty key: one insert covers them all
-        HIP_TRY(c->kslot[0].ensure(16));
-        KeyBatch kb{(const uint8_t*)c->kslot[0].p, nullptr, 0, 1};
-        if (int rc = build_dev(c, kb, num_bits, k, dw, c->st)) return rc;
-        n = 0;
-    }
-    const uint64_t budget = h2d_chunk_bytes();
-    const uint64_t max_keys = 32ull << 20;  // per chunk (bounds the offsets slot)
-    uint64_t f = 0;
-    for (int i = 0; f < n; i++) {
-        const int s = i & 1;
-        uint64_t e;
-        if (offsets) {  // largest e with offsets[e] - offsets[f] <= budget, at least one key
-            const uint64_t* hi = std::upper_bound(offsets + f + 1, offsets + n + 1, offsets[f] + budget);
-            e = std::max<uint64_t>(f + 1, (uint64_t)(hi - offsets) - 1);
-            e = std::min(e, f + max_keys);
-        } else {
-            e = std::min(n, f + std::max<uint64_t>(1, budget / key_len));
-        }
-        const uint64_t m = e - f;
-        const uint64_t base = offsets ? offsets[f] : f * key_len;
-        const uint64_t bytes = offsets ? offsets[e] - offsets[f] : m * key_len;
-        // slot s was last read by chunk i-2's kernels
-        if (i >= 2) HIP_TRY(hipEventSynchronize(c->ev_built[s]));
-        HIP_TRY(c->kslot[s].ensure(std::max<uint64_t>(bytes, std::min(budget, n * (uint64_t)(key_len ? key_len : 1))) + 16));
-        if (bytes) HIP_TRY(hipMemcpyAsync(c->kslot[s].p, data + base, bytes, hipMemcpyHostToDevice, c->cst));
-        if (offsets) {
-            if (c->offs_pin_cap[s] < m + 1) {
-                c->pinned_retired.retire(c->offs_pin[s]);
-                c->offs_pin[s] = nullptr;
-                c->offs_pin_cap[s] = 0;
-                const uint64_t cap = std::max<uint64_t>(m + 1, std::min<uint64_t>(n, max_keys) + 1);
-                if (hipHostMalloc((void**)&c->offs_pin[s], cap * 8, 0) != hipSuccess)
-                    return fail(LSMB_ENOMEM, "pinned offsets staging (%llu B)", (unsigned long long)(cap * 8));
-                c->offs_pin_cap[s] = cap;
-            }
-            uint64_t* o = c->offs_pin[s];
-            for (uint64_t j = 0; j <= m; j++) o[j] = offsets[f + j] - base;
-            HIP_TRY(c->oslot[s].ensure(c->offs_pin_cap[s] * 8));
-            HIP_TRY(hipMemcpyAsync(c->oslot[s].p, o, (m + 1) * 8, hipMemcpyHostToDevice, c->cst));
-        }
-        HIP_TRY(hipEventRecord(c->ev_copy[s], c->cst));
-        HIP_TRY(hipStreamWaitEvent(c->st, c->ev_copy[s], 0));
-        KeyBatch kb{(const uint8_t*)c->kslot[s].p, offsets ? (const uint64_t*)c->oslot[s].p : nullptr, key_len, m};
-        if (int rc = build_dev(c, kb, num_bits, k, dw, c->st)) return rc;
-        HIP_TRY(hipEventRecord(c->ev_built[s], c->st));
-        f = e;
-    }
-    return LSMB_OK;
-}
-
-// crc (optional): CRC-32 of the words appended to *crc (the CRC of the bytes
-// before them), computed on the device copy for device builds.
-int host_build(lsmb_ctx* c, const uint8_t* data, const uint64_t* offsets, uint32_t key_len, uint64_t n,
-               uint32_t num_bits, uint32_t k, const uint64_t* words_in, uint8_t* words_out, uint32_t* crc = nullptr) {
-    const uint64_t nw = nwords64(num_bits);
-    {
-        const uint64_t kb = offsets ? offsets[n] - offsets[0] : n * (uint64_t)key_len;
-        if (kb + (offsets ? (n + 1) * 8 : 0) + nw * 8 <= kSmallHostBuild) {
-            const int rc = host_build_small(c, data, offsets, key_len, n, num_bits, k, words_in, words_out);
-            if (!rc && crc) *crc = crc32_host(words_out, nw * 8, *crc);
-            return rc;
-        }
-    }
-    HIP_TRY(c->words.ensure(nw * 8));
-    uint32_t* dw = (uint32_t*)c->words.p;
-    if (words_in)
-        HIP_TRY(hipMemcpyAsync(dw, words_in, nw * 8, hipMemcpyHostToDevice, c->st));
-    else
-        HIP_TRY(hipMemsetAsync(dw, 0, nw * 8, c->st));
-    if (int rc = host_build_dev(c, data, offsets, key_len, n, num_bits, k, dw)) return rc;
-    HIP_TRY(hipMemcpyAsync(words_out, dw, nw * 8, hipMemcpyDeviceToHost, c->st));
-    if (crc) {
-        if (int rc = crc32_dev(c, (const uint8_t*)dw, nw * 8, *crc, c->st, crc)) return rc;
-    }
-    HIP_TRY(hipStreamSynchronize(c->st));
-    return LSMB_OK;
-}
 
 // The library's own host build: BloomFilter::insert per key
 // (src/bloom/mod.rs:70-78) with the same xxh3 / exact-modulo code the kernels
@@ -454,9 +195,7 @@ int lsmb_serialize(const uint64_t* words, uint32_t num_bits, uint32_t k, uint8_t
     const uint64_t nw = nwords64(num_bits);
     if (out_len < 12 + 8 * nw) return fail(LSMB_EINVAL, "serialize: output buffer too small");
     if (nw && !words) return fail(LSMB_EINVAL, "serialize: null words");
-    const uint32_t hdr[3] = {k, num_bits, (uint32_t)nw};
-    for (int j = 0; j < 3; j++)
-        for (int b = 0; b < 4; b++) out[4 * j + b] = (uint8_t)(hdr[j] >> (8 * b));
+    write_header(out, num_bits, k);
     // words are little-endian u64 on this (x86-64) host: a straight copy.
     if (nw) memcpy(out + 12, words, 8 * nw);
     return LSMB_OK;
@@ -601,30 +340,36 @@ int lsmb_sync(lsmb_ctx* c) {
     return LSMB_OK;
 }
 
-int lsmb_build_fixed_dev(lsmb_ctx* c, const void* d_keys, uint32_t key_len, uint64_t n,
-                         uint32_t num_bits, uint32_t k, void* d_words, void* stream) {
+// The device build entry points: null ctx, then the filter arguments, then
+// null pointers (fresh builds write d_words even with no keys), then the sweep
+// range (sweep builds; NULL: every sweep); then the build on the caller's
+// stream.  kb.n is set here: fixed-length keys of length 0 are all the empty
+// key, one insert covers them.
+static int build_dev_checked(lsmb_ctx* c, KeyBatch kb, bool var, uint64_t n, uint32_t num_bits, uint32_t k,
+                             void* d_words, void* stream, bool fresh, const int* sweep = nullptr) {
     if (!c) return fail(LSMB_EINVAL, "null ctx");
     if (int rc = check_filter(num_bits, k)) return rc;
-    if (n && (!d_keys || !d_words)) return fail(LSMB_EINVAL, "null device pointer");
-    if (n && key_len == 0) {
-        // every key is the empty key: one insert covers them all
-        KeyBatch kb{(const uint8_t*)d_keys, nullptr, 0, 1};
-        DevGuard g(c->dev);
-        return build_dev(c, kb, num_bits, k, (uint32_t*)d_words, pick_stream(c, stream));
+    const void* d_keys = var ? (const void*)kb.offsets : (const void*)kb.data;
+    if (fresh ? (!d_words || (n && !d_keys)) : (n && (!d_keys || !d_words))) return fail(LSMB_EINVAL, "null device pointer");
+    if (sweep) {
+        const int ns = lsmb_build_sweeps(num_bits, k, n);
+        if (*sweep < 0 || *sweep >= ns) return fail(LSMB_EINVAL, "sweep %d out of range [0, %d)", *sweep, ns);
     }
+    kb.n = var || kb.key_len ? n : (n ? 1 : 0);
     DevGuard g(c->dev);
-    KeyBatch kb{(const uint8_t*)d_keys, nullptr, key_len, n};
-    return build_dev(c, kb, num_bits, k, (uint32_t*)d_words, pick_stream(c, stream));
+    return build_dev(c, kb, num_bits, k, (uint32_t*)d_words, pick_stream(c, stream), sweep ? *sweep : -1, fresh);
+}
+
+int lsmb_build_fixed_dev(lsmb_ctx* c, const void* d_keys, uint32_t key_len, uint64_t n,
+                         uint32_t num_bits, uint32_t k, void* d_words, void* stream) {
+    return build_dev_checked(c, KeyBatch{(const uint8_t*)d_keys, nullptr, key_len, 0}, /*var=*/false, n, num_bits, k, d_words, stream,
+                             /*fresh=*/false);
 }
 
 int lsmb_build_var_dev(lsmb_ctx* c, const void* d_data, const void* d_offsets, uint64_t n,
                        uint32_t num_bits, uint32_t k, void* d_words, void* stream) {
-    if (!c) return fail(LSMB_EINVAL, "null ctx");
-    if (int rc = check_filter(num_bits, k)) return rc;
-    if (n && (!d_offsets || !d_words)) return fail(LSMB_EINVAL, "null device pointer");
-    DevGuard g(c->dev);
-    KeyBatch kb{(const uint8_t*)d_data, (const uint64_t*)d_offsets, 0, n};
-    return build_dev(c, kb, num_bits, k, (uint32_t*)d_words, pick_stream(c, stream));
+    return build_dev_checked(c, KeyBatch{(const uint8_t*)d_data, (const uint64_t*)d_offsets, 0, 0}, /*var=*/true, n, num_bits, k,
+                             d_words, stream, /*fresh=*/false);
 }
 
 // BloomFilterBuilder::{new, add_key, build} (src/bloom/builder.rs:14-28): BloomFilter::new
@@ -633,22 +378,14 @@ int lsmb_build_var_dev(lsmb_ctx* c, const void* d_data, const void* d_offsets, u
 // without reading it, so no zeroing pass and no read of the old words.
 int lsmb_build_fixed_dev_new(lsmb_ctx* c, const void* d_keys, uint32_t key_len, uint64_t n, uint32_t num_bits,
                              uint32_t k, void* d_words, void* stream) {
-    if (!c) return fail(LSMB_EINVAL, "null ctx");
-    if (int rc = check_filter(num_bits, k)) return rc;
-    if (!d_words || (n && !d_keys)) return fail(LSMB_EINVAL, "null device pointer");
-    DevGuard g(c->dev);
-    KeyBatch kb{(const uint8_t*)d_keys, nullptr, key_len, key_len ? n : (n ? 1 : 0)};
-    return build_dev(c, kb, num_bits, k, (uint32_t*)d_words, pick_stream(c, stream), -1, /*fresh=*/true);
+    return build_dev_checked(c, KeyBatch{(const uint8_t*)d_keys, nullptr, key_len, 0}, /*var=*/false, n, num_bits, k, d_words, stream,
+                             /*fresh=*/true);
 }
 
 int lsmb_build_var_dev_new(lsmb_ctx* c, const void* d_data, const void* d_offsets, uint64_t n, uint32_t num_bits,
                            uint32_t k, void* d_words, void* stream) {
-    if (!c) return fail(LSMB_EINVAL, "null ctx");
-    if (int rc = check_filter(num_bits, k)) return rc;
-    if (!d_words || (n && !d_offsets)) return fail(LSMB_EINVAL, "null device pointer");
-    DevGuard g(c->dev);
-    KeyBatch kb{(const uint8_t*)d_data, (const uint64_t*)d_offsets, 0, n};
-    return build_dev(c, kb, num_bits, k, (uint32_t*)d_words, pick_stream(c, stream), -1, /*fresh=*/true);
+    return build_dev_checked(c, KeyBatch{(const uint8_t*)d_data, (const uint64_t*)d_offsets, 0, 0}, /*var=*/true, n, num_bits, k,
+                             d_words, stream, /*fresh=*/true);
 }
 
 // Builds of n <= host_max_keys() keys run the library's host loop (no device
@@ -661,9 +398,10 @@ static int need_ctx(lsmb_ctx* c, uint64_t n) {
     return LSMB_OK;
 }
 
+// (the sweep layout is a function of (num_bits, k): no device needed)
 int lsmb_build_sweeps(uint32_t num_bits, uint32_t k, uint64_t n) {
     if (pick_build_strategy(num_bits, k, n) != BuildStrategy::Partition) return 1;
-    return (int)plan_partition(num_bits, k, n, 256).sweeps;
+    return (int)partition_layout(num_bits, k).sweeps;
 }
 
 int lsmb_sweep_words(uint32_t num_bits, uint32_t k, uint64_t n, int sweep, uint64_t* word_lo, uint64_t* word_hi) {
@@ -676,7 +414,7 @@ int lsmb_sweep_words(uint32_t num_bits, uint32_t k, uint64_t n, int sweep, uint6
         *word_hi = nw;
         return LSMB_OK;
     }
-    const PartitionPlan pl = plan_partition(num_bits, k, n, 256);
+    const PartitionPlan pl = partition_layout(num_bits, k);
     const uint64_t w_per_slice = (1ull << pl.slice_log2) / 64;
     *word_lo = std::min<uint64_t>(nw, (uint64_t)sweep * pl.bins_per_sweep * w_per_slice);
     *word_hi = std::min<uint64_t>(nw, ((uint64_t)sweep + 1) * pl.bins_per_sweep * w_per_slice);
@@ -685,26 +423,14 @@ int lsmb_sweep_words(uint32_t num_bits, uint32_t k, uint64_t n, int sweep, uint6
 
 int lsmb_build_fixed_dev_sweep(lsmb_ctx* c, const void* d_keys, uint32_t key_len, uint64_t n, uint32_t num_bits,
                                uint32_t k, void* d_words, int sweep, void* stream) {
-    if (!c) return fail(LSMB_EINVAL, "null ctx");
-    if (int rc = check_filter(num_bits, k)) return rc;
-    if (n && (!d_keys || !d_words)) return fail(LSMB_EINVAL, "null device pointer");
-    const int ns = lsmb_build_sweeps(num_bits, k, n);
-    if (sweep < 0 || sweep >= ns) return fail(LSMB_EINVAL, "sweep %d out of range [0, %d)", sweep, ns);
-    DevGuard g(c->dev);
-    KeyBatch kb{(const uint8_t*)d_keys, nullptr, key_len, key_len ? n : (n ? 1 : 0)};
-    return build_dev(c, kb, num_bits, k, (uint32_t*)d_words, pick_stream(c, stream), sweep);
+    return build_dev_checked(c, KeyBatch{(const uint8_t*)d_keys, nullptr, key_len, 0}, /*var=*/false, n, num_bits, k, d_words, stream,
+                             /*fresh=*/false, &sweep);
 }
 
 int lsmb_build_fixed_dev_sweep_new(lsmb_ctx* c, const void* d_keys, uint32_t key_len, uint64_t n, uint32_t num_bits,
                                    uint32_t k, void* d_words, int sweep, void* stream) {
-    if (!c) return fail(LSMB_EINVAL, "null ctx");
-    if (int rc = check_filter(num_bits, k)) return rc;
-    if (!d_words || (n && !d_keys)) return fail(LSMB_EINVAL, "null device pointer");
-    const int ns = lsmb_build_sweeps(num_bits, k, n);
-    if (sweep < 0 || sweep >= ns) return fail(LSMB_EINVAL, "sweep %d out of range [0, %d)", sweep, ns);
-    DevGuard g(c->dev);
-    KeyBatch kb{(const uint8_t*)d_keys, nullptr, key_len, key_len ? n : (n ? 1 : 0)};
-    return build_dev(c, kb, num_bits, k, (uint32_t*)d_words, pick_stream(c, stream), sweep, /*fresh=*/true);
+    return build_dev_checked(c, KeyBatch{(const uint8_t*)d_keys, nullptr, key_len, 0}, /*var=*/false, n, num_bits, k, d_words, stream,
+                             /*fresh=*/true, &sweep);
 }
 
 int lsmb_build_fixed(lsmb_ctx* c, const uint8_t* keys, uint32_t key_len, uint64_t n, uint32_t num_bits,
@@ -750,10 +476,7 @@ static int build_block(lsmb_ctx* c, const uint8_t* data, const uint64_t* offsets
     if (n && offsets) {
         if (int rc = check_offsets(offsets, n)) return rc;
     }
-    // header of BloomFilter::serialize (src/bloom/mod.rs:102-115)
-    const uint32_t hdr[3] = {k, num_bits, (uint32_t)nw};
-    for (int i = 0; i < 3; i++)
-        for (int b = 0; b < 4; b++) block[4 * i + b] = (uint8_t)(hdr[i] >> (8 * b));
+    write_header(block, num_bits, k);
     if (n == 0 || k == 0) {  // new() + no inserts: all-zero words
         memset(block + 12, 0, nw * 8);
         if (crc) *crc = crc32_host(block, size, 0);

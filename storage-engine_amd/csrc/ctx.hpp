@@ -1,5 +1,6 @@
 // ctx.hpp — the per-GPU context behind lsmb_ctx and the host plumbing shared by
-// capi.hip (single GPU) and multi.hip (one process, several GPUs).  Internal.
+// capi.hip (the C ABI), build_dev.hip (build orchestration), stream.hip and
+// multi.hip (one process, several GPUs).  Internal.
 #pragma once
 
 #include <stdint.h>
@@ -145,6 +146,12 @@ int build_dev(lsmb_ctx* c, const KeyBatch& kb, uint32_t num_bits, uint32_t k, ui
 // enqueued; the caller synchronises c->st.
 int host_build_dev(lsmb_ctx* c, const uint8_t* data, const uint64_t* offsets, uint32_t key_len, uint64_t n,
                    uint32_t num_bits, uint32_t k, uint32_t* dw);
+
+// Synchronous build from keys in host memory: words_in == NULL starts from a
+// zeroed filter, else from those words; the finished words go to words_out
+// (host, any alignment).  crc (optional): CRC-32 of the words appended to *crc.
+int host_build(lsmb_ctx* c, const uint8_t* data, const uint64_t* offsets, uint32_t key_len, uint64_t n,
+               uint32_t num_bits, uint32_t k, const uint64_t* words_in, uint8_t* words_out, uint32_t* crc = nullptr);
 
 // Host build (the library's native per-key loop) into words (OR-accumulate).
 void host_insert_batch(const uint8_t* data, const uint64_t* offsets, uint32_t key_len, uint64_t n,

@@ -67,6 +67,12 @@ struct PartitionPlan {
     uint64_t counts_bytes = 0;    // nbins * grid * 4
 };
 
+// The plan in two steps (build_plan.hip).  The layout — slice_log2, nbins,
+// bins_per_sweep, ring, sweeps, keys_per_lane — is a function of (num_bits, k)
+// alone, so build_sweeps / sweep_words answer without a device; the capacity
+// — grid, cap_segs and the byte sizes — of (layout, n, num_cus).
+PartitionPlan partition_layout(uint32_t num_bits, uint32_t k);
+PartitionPlan partition_capacity(PartitionPlan layout, uint32_t num_bits, uint32_t k, uint64_t n, int num_cus);
 PartitionPlan plan_partition(uint32_t num_bits, uint32_t k, uint64_t n, int num_cus);
 
 // Tiled strategy (filters of 2..kTiledMaxSlices slices): workgroup (c, s)
@@ -83,25 +89,42 @@ TiledPlan plan_tiled(uint32_t num_bits, uint64_t n, int num_cus);
 // Largest key count whose plan fits `max_bytes` of workspace.
 uint64_t partition_chunk_keys(uint32_t num_bits, uint32_t k, uint64_t max_bytes, int num_cus);
 
+// Bytes per workspace buffer: what a build needs (workspace_bytes) and what
+// it was handed (PartitionWorkspace::have).
+struct WorkspaceBytes {
+    uint64_t regions = 0;  // partition: the regions; tiled: the scratch tiles
+    uint64_t counts = 0;   // partition: segments written per region
+    uint64_t hashes = 0;   // 16 B per key (partition builds store 12-B walk records in them)
+    uint64_t ovf = 0;      // fresh k = 7 partition builds: overflow words of the whole filter,
+    uint64_t dirty = 0;    //   one mark per 2^20-bit unit of them,
+    uint64_t ovl = 0;      //   kOvfListCap overflow positions per pass A workgroup per sweep
+    uint64_t ovn = 0;      //   and each list's length
+    bool covers(const WorkspaceBytes& need) const {
+        return regions >= need.regions && counts >= need.counts && hashes >= need.hashes && ovf >= need.ovf &&
+               dirty >= need.dirty && ovl >= need.ovl && ovn >= need.ovn;
+    }
+};
+
+// The one workspace contract: build_dev.hip allocates by it, launch_build
+// validates by it.  n = the keys of one launch_build call (a chunk); aligned16
+// = 16-B keys on a 16-B-aligned base (pass A hashes them inline).
+WorkspaceBytes workspace_bytes(BuildStrategy s, const PartitionPlan& pl, const TiledPlan& tp, uint32_t num_bits,
+                               uint32_t k, uint64_t n, bool aligned16, bool fresh);
+
 struct PartitionWorkspace {
-    uint4* hashes = nullptr;  // 16 B per key: k_hash output for var-len / odd-length keys
-    uint64_t hash_bytes = 0;
+    uint4* hashes = nullptr;  // k_hash output for var-len / odd-length keys
     uint64_t* regions = nullptr;
     uint32_t* counts = nullptr;
     uint32_t* err = nullptr;  // device flag, see PassA::err
     // Pass A's overflow bits (ring / region overflow, adversarial inputs) and
     // per-2^20-bit-unit marks, both all-zero between builds (pass B clears
-    // what it consumes): ovf_units * 2^15 u32 words, ovf_units marks.
+    // what it consumes)
     uint32_t* ovf = nullptr;
     uint32_t* dirty = nullptr;
-    uint64_t ovf_units = 0;
-    // fresh builds: per pass A workgroup, a list of kOvfListCap overflow
-    // positions and its length (ovl_groups workgroups' worth)
+    // fresh builds: the overflow position lists and their lengths
     uint32_t* ovl = nullptr;
     uint32_t* ovn = nullptr;
-    uint32_t ovl_groups = 0;
-    uint64_t region_bytes = 0;
-    uint64_t counts_bytes = 0;
+    WorkspaceBytes have;  // bytes behind each pointer above
 };
 
 struct BuildTimers {
@@ -111,8 +134,8 @@ struct BuildTimers {
 
 // Builds into d_words32 (OR-accumulate; fresh: BloomFilter::new + inserts,
 // the words are output-only and every word of the build's range is written).
-// For the Partition strategy the workspace must hold plan_partition(num_bits,
-// k, kb.n, num_cus) and the overflow words of the whole filter.  Records
+// The workspace must cover workspace_bytes() of this call (the tiled hash
+// records are optional: without them the tiles hash the keys).  Records
 // t0/t1/t2 (start / pass A done / end) when timers != NULL.  sweep >= 0
 // builds only the bits of that partition sweep's slices (sweep 0 = the whole
 // build for the other strategies; see build_sweeps / sweep_words).

@@ -267,6 +267,27 @@ def test_walk_records_replay_the_walks(tmp_path):
     assert out.returncode == 0, out.stdout + out.stderr
 
 
+def test_build_plan_table(tmp_path):
+    """The host build planner (csrc/build_plan.hip: strategy, partition and
+    tiled plans, workspace-bounded chunk sizes) reproduces its recorded table
+    (tests/golden/plan_table.json) row for row, its layout depends on
+    (num_bits, k) alone and fits pass A's LDS (tests/cpp/plan_test.cpp, a host
+    program linked with the planner; the plan's measurement knobs unset)."""
+    import subprocess
+    exe = str(tmp_path / "plan_test")
+    srcs = [os.path.join(ROOT, "tests", "cpp", "plan_test.cpp"),
+            os.path.join(ROOT, "storage-engine_amd", "csrc", "build_plan.hip")]
+    r = subprocess.run(["/opt/rocm/bin/hipcc", "-O2", "-std=c++17", "--offload-arch=gfx950", *srcs, "-o", exe],
+                       capture_output=True, text=True)
+    assert r.returncode == 0, r.stderr[-3000:]
+    env = {k: v for k, v in os.environ.items()
+           if k not in ("LSMB_SLICE_LOG2", "LSMB_SWEEP_PER", "LSMB_BIN_WGS_PER_CU")}
+    out = subprocess.run([exe, os.path.join(ROOT, "tests", "golden", "plan_table.json")], capture_output=True,
+                         text=True, timeout=120, env=env)
+    assert out.returncode == 0, out.stdout[-3000:] + out.stderr
+    assert "1890 rows, 0 bad" in out.stdout
+
+
 def test_reductions_at_quotient_edges(tmp_path):
     """Mod32::reduce, Mod32::reduce31 (Walk32's 32-bit remainder path) and
     Mod14::reduce against a literal 64-bit % at the inputs that stress their
