@@ -466,6 +466,27 @@ int lsmb_fset_probe_dev(lsmb_fset* fs, const void* d_data, const void* d_offsets
 int lsmb_fset_probe_dev_rows(lsmb_fset* fs, const void* d_data, const void* d_offsets, uint32_t key_len, uint64_t n,
                              void* d_out, uint32_t row_bytes, void* stream);
 
+/* The answer per table instead of per key: what a reader that works table by
+ * table wants (open table s, look up the keys that may be in it, close it).
+ * For every slot s < 64: d_index[d_starts[s] .. d_starts[s+1]) = the indices i
+ * (ascending) of the keys with bit s set in lsmb_fset_probe's mask, i.e.
+ * (min_s <= key i <= max_s) && may_contain(filter s, key i).  d_starts is
+ * uint64_t[65]; d_starts[0] = 0; d_starts[64] = total entries; a dead slot's run
+ * is empty.  d_index is uint32_t[cap].  d_starts is always exact; the entry at
+ * global position p is written iff p < cap, nothing else in d_index is
+ * touched, so a caller whose d_starts[64] > cap learns the size it needs
+ * (cap == 0 with a null d_index is a counting call).  n == 0 or an empty set
+ * writes 65 zero starts.  n > 2^32-1: LSMB_EINVAL.  Asynchronous on `stream`.
+ * The mask rows and per-tile counts in between live in the set's own scratch:
+ * lists probes on different streams run one after the other. */
+int lsmb_fset_probe_lists_dev(lsmb_fset* fs, const void* d_data, const void* d_offsets, uint32_t key_len,
+                              uint64_t n, void* d_starts, void* d_index, uint64_t cap, void* stream);
+
+/* Host keys and host outputs (starts[65], index[cap]); synchronous.  Only
+ * starts and min(total, cap) entries cross PCIe on the way back. */
+int lsmb_fset_probe_lists(lsmb_fset* fs, const uint8_t* data, const uint64_t* offsets, uint32_t key_len,
+                          uint64_t n, uint64_t* starts, uint32_t* index, uint64_t cap);
+
 /* ---- introspection ------------------------------------------------------- */
 
 /* Name of the device build strategy the dispatcher picks for (num_bits, k, n):

@@ -21,6 +21,7 @@
 
 #include <stdint.h>
 
+#include <array>
 #include <memory>
 #include <stdexcept>
 #include <string>
@@ -222,6 +223,32 @@ class FilterSet {
         std::vector<uint64_t> out(keys.size());
         check(lsmb_fset_probe(fs_, u8(data), offs.data(), 0, keys.size(), out.data()));
         return out;
+    }
+
+    // The answer per table (lsmb_fset_probe_lists): index[starts[s] ..
+    // starts[s+1]) = the ascending indices of the keys with bit s set in
+    // probe()'s mask.  Sized for one entry per key; a longer answer takes one
+    // more call with the size the first one reported.
+    struct Lists {
+        std::array<uint64_t, 65> starts;
+        std::vector<uint32_t> index;
+    };
+    Lists probe_lists(const std::vector<std::string>& keys) {
+        std::vector<uint64_t> offs(keys.size() + 1, 0);
+        std::string data;
+        for (size_t i = 0; i < keys.size(); i++) {
+            data += keys[i];
+            offs[i + 1] = data.size();
+        }
+        Lists out;
+        out.index.resize(keys.size());
+        for (;;) {
+            const uint64_t cap = out.index.size();
+            check(lsmb_fset_probe_lists(fs_, u8(data), offs.data(), 0, keys.size(), out.starts.data(),
+                                        out.index.data(), cap));
+            out.index.resize(out.starts[64]);
+            if (out.starts[64] <= cap) return out;
+        }
     }
 
    private:

@@ -705,6 +705,15 @@ struct lsmb_fset {
     // whole device, so another context's builds keep running.
     hipStream_t ust = nullptr;
     std::vector<std::pair<hipStream_t, hipEvent_t>> probe_ev;
+    // Lists probes (lsmb_fset_probe_lists*): the mask rows and the per-tile
+    // counts are the set's own scratch, shared by every lists probe whatever
+    // its stream.  lists_ev (one of probe_ev's events) is completed by the
+    // last lists probe's last kernel on lists_stream; a lists probe on
+    // another stream waits for it first.
+    DevBuf lrows, ltiles;
+    DevBuf lstarts, lindex;  // device outputs of the host-memory entry point
+    hipStream_t lists_stream = nullptr;
+    hipEvent_t lists_ev = nullptr;
 };
 
 namespace {
@@ -952,6 +961,10 @@ void lsmb_fset_close(lsmb_fset* fs) {
         fs->ranges.release();
         fs->points.release();
         fs->desc.release();
+        fs->lrows.release();
+        fs->ltiles.release();
+        fs->lstarts.release();
+        fs->lindex.release();
     }
     delete fs;
 }
@@ -1047,6 +1060,82 @@ int lsmb_fset_probe(lsmb_fset* fs, const uint8_t* data, const uint64_t* offsets,
                               (uint8_t*)c->out.p, 8, c->num_cus, c->st, ev));
     HIP_TRY(hipMemcpyAsync(out_mask, c->out.p, n * 8, hipMemcpyDeviceToHost, c->st));
     HIP_TRY(hipStreamSynchronize(c->st));
+    return LSMB_OK;
+}
+
+// The lists probe on `st` over device keys: the mask probe into the set's row
+// scratch (the narrowest rows that hold every live slot), then the three
+// compaction kernels (fset_lists.hip).  kb.n >= 1.
+static int fset_lists_dev(lsmb_fset* fs, const KeyBatch& kb, uint64_t* d_starts, uint32_t* d_index, uint64_t cap,
+                          hipStream_t st) {
+    if (int rc = fset_refresh(fs)) return rc;
+    if (fs->ndesc == 0) {
+        HIP_TRY(hipMemsetAsync(d_starts, 0, 65 * 8, st));
+        return LSMB_OK;
+    }
+    const uint64_t live = lsmb_fset_live_mask(fs);
+    const uint32_t rb = (live >> 8) == 0 ? 1 : (live >> 16) == 0 ? 2 : (live >> 32) == 0 ? 4 : 8;
+    hipEvent_t ev;
+    if (int rc = fset_probe_event(fs, st, &ev)) return rc;
+    // the scratch is the previous lists probe's too: in order on its stream,
+    // after its last kernel on any other
+    if (fs->lists_ev && fs->lists_stream != st) HIP_TRY(hipStreamWaitEvent(st, fs->lists_ev, 0));
+    HIP_TRY(fs->lrows.ensure(kb.n * rb));
+    HIP_TRY(fs->ltiles.ensure(fset_lists_tile_bytes(kb.n, live)));
+    fs->lists_stream = st;
+    fs->lists_ev = ev;
+    hipError_t e = launch_fset_probe(kb, (const RangedFilter*)fs->desc.p, fs->ndesc, fs->rg, fs->cl, fs->shared_nb,
+                                     fs->shared_k, (uint8_t*)fs->lrows.p, rb, fs->c->num_cus, st);
+    if (e == hipSuccess)
+        e = launch_fset_lists((const uint8_t*)fs->lrows.p, rb, kb.n, live, (uint32_t*)fs->ltiles.p, d_starts, d_index,
+                              cap, st, ev);  // (its last dispatch completes the guard event)
+    if (e != hipSuccess) {
+        (void)hipEventRecord(ev, st);  // whatever was launched still reads the set's buffers
+        return hip_fail(e, "filter set lists probe");
+    }
+    return LSMB_OK;
+}
+
+int lsmb_fset_probe_lists_dev(lsmb_fset* fs, const void* d_data, const void* d_offsets, uint32_t key_len, uint64_t n,
+                              void* d_starts, void* d_index, uint64_t cap, void* stream) {
+    if (!fs) return fail(LSMB_EINVAL, "null filter set");
+    if (n > UINT32_MAX) return fail(LSMB_EINVAL, "more than 2^32-1 keys (the lists hold 32-bit indices)");
+    if (!d_starts || (cap && !d_index)) return fail(LSMB_EINVAL, "null output");
+    if (n && !d_data) return fail(LSMB_EINVAL, "null keys");
+    DevGuard g(fs->c->dev);
+    const hipStream_t st = pick_stream(fs->c, stream);
+    if (n == 0) {
+        HIP_TRY(hipMemsetAsync(d_starts, 0, 65 * 8, st));
+        return LSMB_OK;
+    }
+    KeyBatch kb{(const uint8_t*)d_data, (const uint64_t*)d_offsets, key_len, n};
+    return fset_lists_dev(fs, kb, (uint64_t*)d_starts, (uint32_t*)d_index, cap, st);
+}
+
+int lsmb_fset_probe_lists(lsmb_fset* fs, const uint8_t* data, const uint64_t* offsets, uint32_t key_len, uint64_t n,
+                          uint64_t* starts, uint32_t* index, uint64_t cap) {
+    if (!fs) return fail(LSMB_EINVAL, "null filter set");
+    if (n > UINT32_MAX) return fail(LSMB_EINVAL, "more than 2^32-1 keys (the lists hold 32-bit indices)");
+    if (!starts || (cap && !index)) return fail(LSMB_EINVAL, "null output");
+    if (n && !data && (offsets ? offsets[n] > offsets[0] : key_len > 0)) return fail(LSMB_EINVAL, "null keys");
+    memset(starts, 0, 65 * 8);
+    if (n == 0 || lsmb_fset_live_mask(fs) == 0) return LSMB_OK;
+    lsmb_ctx* c = fs->c;
+    DevGuard g(c->dev);
+    KeyBatch kb;
+    if (int rc = stage_host_keys(c, data, offsets, key_len, n, &kb)) return rc;
+    // no list is longer than the live slots' n entries each
+    const uint64_t dcap = std::min<uint64_t>(cap, n * 64);
+    HIP_TRY(fs->lstarts.ensure(65 * 8));
+    HIP_TRY(fs->lindex.ensure(std::max<uint64_t>(dcap, 1) * 4));
+    if (int rc = fset_lists_dev(fs, kb, (uint64_t*)fs->lstarts.p, (uint32_t*)fs->lindex.p, dcap, c->st)) return rc;
+    HIP_TRY(hipMemcpyAsync(starts, fs->lstarts.p, 65 * 8, hipMemcpyDeviceToHost, c->st));
+    HIP_TRY(hipStreamSynchronize(c->st));
+    const uint64_t got = std::min<uint64_t>(starts[64], dcap);
+    if (got) {
+        HIP_TRY(hipMemcpyAsync(index, fs->lindex.p, got * 4, hipMemcpyDeviceToHost, c->st));
+        HIP_TRY(hipStreamSynchronize(c->st));
+    }
     return LSMB_OK;
 }
 

@@ -213,6 +213,19 @@ hipError_t launch_fset_probe(const KeyBatch& kb, const RangedFilter* d_filters, 
                              const FsetClasses& cl, uint32_t shared_nb, uint32_t shared_k, uint8_t* d_out_rows,
                              uint32_t row_bytes, int num_cus, hipStream_t st, hipEvent_t done = nullptr);
 
+// The probe's answer transposed (fset_lists.hip): from the n mask rows of
+// launch_fset_probe (row_bytes each, every slot of `live` within them), for
+// every slot s < 64, d_index[d_starts[s] .. d_starts[s+1]) = the ascending
+// indices of the rows with bit s set; d_starts[65] is always exact, the entry
+// at position p is stored iff p < cap.  d_tiles: fset_lists_tile_bytes(n,
+// live) bytes of scratch (per-tile counts, then offsets), 16-B aligned.
+// 1 <= n <= 2^32-1, live != 0.  done: completed by the last kernel.
+constexpr uint32_t kListTile = 1024;  // keys per workgroup
+uint64_t fset_lists_tile_bytes(uint64_t n, uint64_t live);
+hipError_t launch_fset_lists(const uint8_t* d_rows, uint32_t row_bytes, uint64_t n, uint64_t live, uint32_t* d_tiles,
+                             uint64_t* d_starts, uint32_t* d_index, uint64_t cap, hipStream_t st,
+                             hipEvent_t done = nullptr);
+
 // A kernel launch whose completion also completes `done` (when non-null):
 // hipExtLaunchKernelGGL tracks the event with the dispatch's own completion
 // signal, where hipEventRecord after the launch would put a marker packet in

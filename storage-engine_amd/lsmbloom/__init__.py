@@ -90,6 +90,10 @@ SIGNATURES = {
     "lsmb_fset_probe": (ctypes.c_int, [vp, u8p, u64p, ctypes.c_uint32, ctypes.c_uint64, u64p]),
     "lsmb_fset_probe_dev": (ctypes.c_int, [vp, vp, vp, ctypes.c_uint32, ctypes.c_uint64, vp, vp]),
     "lsmb_fset_probe_dev_rows": (ctypes.c_int, [vp, vp, vp, ctypes.c_uint32, ctypes.c_uint64, vp, ctypes.c_uint32, vp]),
+    "lsmb_fset_probe_lists_dev": (ctypes.c_int, [vp, vp, vp, ctypes.c_uint32, ctypes.c_uint64, vp, vp, ctypes.c_uint64,
+                                                 vp]),
+    "lsmb_fset_probe_lists": (ctypes.c_int, [vp, u8p, u64p, ctypes.c_uint32, ctypes.c_uint64, u64p, u32p,
+                                             ctypes.c_uint64]),
     "lsmb_build_strategy": (ctypes.c_char_p, [ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint64]),
     "lsmb_host_max_keys": (ctypes.c_uint64, []),
     "lsmb_build_sweeps": (ctypes.c_int, [ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint64]),
@@ -613,6 +617,49 @@ class FilterSet:
         else:
             _check(lib().lsmb_fset_probe_dev_rows(self.h, vp(data.data_ptr()), offs, key_len, n, vp(out.data_ptr()),
                                                   int(row_bytes), Context._stream(stream)))
+
+    def probe_lists(self, data, offsets=None, key_len=0, cap=None):
+        """Packed host keys (as probe) -> (starts uint64[65], index uint32[total]):
+        index[starts[s]:starts[s+1]] = the ascending indices of the keys with
+        bit s set in probe()'s mask (lsmb_fset_probe_lists).  cap (default n)
+        sizes the first call; a longer answer takes one more with cap = total."""
+        data = np.ascontiguousarray(data, dtype=np.uint8).reshape(-1)
+        if offsets is not None:
+            offsets = np.ascontiguousarray(offsets, dtype=np.uint64)
+            n = offsets.size - 1
+            op = _p(offsets, u64p)
+        else:
+            n = data.size // key_len if key_len else 0
+            op = None
+        if data.size == 0:
+            data = np.zeros(1, np.uint8)
+        starts = np.zeros(65, dtype=np.uint64)
+        cap = n if cap is None else int(cap)
+        while True:
+            index = np.empty(max(cap, 1), dtype=np.uint32)
+            _check(lib().lsmb_fset_probe_lists(self.h, _p(data, u8p), op, key_len, n, _p(starts, u64p),
+                                               _p(index, u32p), cap))
+            total = int(starts[64])
+            if total <= cap:
+                return starts, index[:total]
+            cap = total
+
+    def probe_lists_keys(self, keys):
+        """list of bytes -> (starts, index) as probe_lists."""
+        lens = np.array([len(k) for k in keys], dtype=np.uint64)
+        offs = np.zeros(len(keys) + 1, dtype=np.uint64)
+        np.cumsum(lens, out=offs[1:])
+        return self.probe_lists(np.frombuffer(b"".join(bytes(k) for k in keys), dtype=np.uint8), offs)
+
+    def probe_lists_dev(self, data, n, starts, index, offsets=None, key_len=0, stream=None):
+        """Device keys -> device lists (lsmb_fset_probe_lists_dev): starts an
+        int64 / uint64 tensor of 65, index an int32 / uint32 tensor whose
+        length is the capacity (None: a counting call).  starts is always
+        exact; entries at positions at and past the capacity are not written."""
+        offs = vp(offsets.data_ptr()) if offsets is not None else None
+        cap = int(index.numel()) if index is not None else 0
+        _check(lib().lsmb_fset_probe_lists_dev(self.h, vp(data.data_ptr()), offs, key_len, n, vp(starts.data_ptr()),
+                                               vp(index.data_ptr()) if cap else None, cap, Context._stream(stream)))
 
 
 def build_strategy(num_bits, n, k=7):
