@@ -487,6 +487,65 @@ int lsmb_fset_probe_lists_dev(lsmb_fset* fs, const void* d_data, const void* d_o
 int lsmb_fset_probe_lists(lsmb_fset* fs, const uint8_t* data, const uint64_t* offsets, uint32_t key_len,
                           uint64_t n, uint64_t* starts, uint32_t* index, uint64_t cap);
 
+/* ---- device-resident level sets (the non-overlapping levels) --------------- */
+/* An lsmb_lset is an immutable snapshot of the store's levels below L0, one
+ * per Version: up to LSMB_LSET_MAX_LEVELS rows, each holding any number of
+ * SSTable filters (bounded by memory and uint32_t) whose key ranges
+ * [min_key, max_key] are pairwise disjoint, as DB::get relies on for those
+ * levels (src/db/mod.rs:255-267, "L1+: no overlaps, at most one SSTable
+ * contains the key").  So the answer per key and row is one table or none, and
+ * a probe writes a caller-chosen table id (the SST id, meta.id) instead of a
+ * mask bit per table: a row of thousands of tables costs each key one binary
+ * search, one range check and at most one filter walk.  Filters may have any
+ * (num_bits, num_hashes), num_hashes = 0 and > 8 included.
+ *   open -> add / add_words (any order) -> seal -> probe ... -> close
+ * A set belongs to one context.  Adds and seal are used from one thread at a
+ * time; a sealed set is only read, so probes on different streams need no
+ * ordering among themselves.  Close a set once its probes have completed. */
+typedef struct lsmb_lset lsmb_lset;
+#define LSMB_LSET_MAX_LEVELS 8
+#define LSMB_LSET_NONE 0xFFFFFFFFu /* the probe's "no table of this row" */
+
+int lsmb_lset_open(lsmb_ctx* ctx, lsmb_lset** out);
+void lsmb_lset_close(lsmb_lset* ls);
+
+/* Adds table `table_id` to row `row` from its serialized bloom block, validated
+ * exactly as lsmb_fset_add does (LSMB_ECORRUPT) and copied to device memory
+ * before the call returns.  LSMB_EINVAL: row >= LSMB_LSET_MAX_LEVELS, table_id
+ * == LSMB_LSET_NONE, num_bits == 0 with num_hashes > 0, an add after seal. */
+int lsmb_lset_add(lsmb_lset* ls, uint32_t row, uint32_t table_id, const uint8_t* block, uint64_t len,
+                  const uint8_t* min_key, uint64_t min_len, const uint8_t* max_key, uint64_t max_len);
+
+/* Same from in-memory filter words (ceil(num_bits/64) LE u64). */
+int lsmb_lset_add_words(lsmb_lset* ls, uint32_t row, uint32_t table_id, const uint64_t* words, uint32_t num_bits,
+                        uint32_t num_hashes, const uint8_t* min_key, uint64_t min_len, const uint8_t* max_key,
+                        uint64_t max_len);
+
+/* Sorts every row by min_key, checks min_t <= max_t for every table and
+ * max_t < min_{t+1} strictly between neighbours (byte-wise, a proper prefix
+ * first, as Rust's [u8] Ord) and uploads the sorted descriptors.  A row that
+ * fails is LSMB_EINVAL, lsmb_last_error() naming the two offending table ids;
+ * the set stays unsealed.  A set with no table seals too. */
+int lsmb_lset_seal(lsmb_lset* ls);
+
+/* 1 + the highest row added (0 when empty; 0 for NULL). */
+int lsmb_lset_rows(const lsmb_lset* ls);
+/* Tables of one row (0 for NULL or a row >= LSMB_LSET_MAX_LEVELS). */
+uint64_t lsmb_lset_tables(const lsmb_lset* ls, uint32_t row);
+
+/* With R = lsmb_lset_rows(ls), out holds R * n values, row-major by level:
+ * out[r*n + i] = table_id of the one table t of row r with
+ *     min_t <= key i <= max_t && may_contain(filter t, key i),
+ * else LSMB_LSET_NONE (an empty row answers LSMB_LSET_NONE everywhere).
+ * n == 0 or R == 0 writes nothing.  offsets == NULL selects fixed-length keys
+ * of key_len bytes.  Before seal: LSMB_EINVAL.  Host keys; synchronous. */
+int lsmb_lset_probe(lsmb_lset* ls, const uint8_t* data, const uint64_t* offsets, uint32_t key_len, uint64_t n,
+                    uint32_t* out);
+
+/* Device-memory keys and output (R * n uint32_t); asynchronous on `stream`. */
+int lsmb_lset_probe_dev(lsmb_lset* ls, const void* d_data, const void* d_offsets, uint32_t key_len, uint64_t n,
+                        void* d_out, void* stream);
+
 /* ---- introspection ------------------------------------------------------- */
 
 /* Name of the device build strategy the dispatcher picks for (num_bits, k, n):

@@ -256,4 +256,54 @@ class FilterSet {
     lsmb_fset* fs_ = nullptr;
 };
 
+// Device-resident snapshot of the store's non-overlapping levels (lsmb_lset),
+// one per Version: rows of tables with pairwise disjoint key ranges, any
+// number per row.  add in any order, seal(), then probe(keys)[r * n + i] =
+// the table_id of the one table t of row r with min_t <= key i <= max_t &&
+// may_contain(filter t, key i), else LSMB_LSET_NONE (the walk of L1 and below
+// in DB::get, src/db/mod.rs:255-267).
+class LevelSet {
+   public:
+    explicit LevelSet(Context& ctx = Context::shared()) { check(lsmb_lset_open(ctx.get(), &ls_)); }
+    ~LevelSet() { lsmb_lset_close(ls_); }
+    LevelSet(const LevelSet&) = delete;
+    LevelSet& operator=(const LevelSet&) = delete;
+
+    // From a serialized bloom block (throws Corruption like deserialize).
+    void add(uint32_t row, uint32_t table_id, const std::vector<uint8_t>& block, std::string_view min_key,
+             std::string_view max_key) {
+        check(lsmb_lset_add(ls_, row, table_id, block.data(), block.size(), u8(min_key), min_key.size(), u8(max_key),
+                            max_key.size()));
+    }
+    void add(uint32_t row, uint32_t table_id, const BloomFilter& f, std::string_view min_key, std::string_view max_key) {
+        check(lsmb_lset_add_words(ls_, row, table_id, f.words().data(), f.num_bits(), f.num_hashes(), u8(min_key),
+                                  min_key.size(), u8(max_key), max_key.size()));
+    }
+    // Sorts and checks the rows (std::invalid_argument naming two overlapping tables).
+    void seal() { check(lsmb_lset_seal(ls_)); }
+    int rows() const { return lsmb_lset_rows(ls_); }
+    uint64_t tables(uint32_t row) const { return lsmb_lset_tables(ls_, row); }
+
+    std::vector<uint32_t> probe(const std::vector<std::string>& keys) {
+        std::vector<uint64_t> offs(keys.size() + 1, 0);
+        std::string data;
+        for (size_t i = 0; i < keys.size(); i++) {
+            data += keys[i];
+            offs[i + 1] = data.size();
+        }
+        std::vector<uint32_t> out(static_cast<size_t>(rows()) * keys.size());
+        check(lsmb_lset_probe(ls_, u8(data), offs.data(), 0, keys.size(), out.data()));
+        return out;
+    }
+    // Device keys and output (rows() * n uint32_t), asynchronous on `stream`.
+    void probe_dev(const void* d_data, const void* d_offsets, uint32_t key_len, uint64_t n, void* d_out,
+                   void* stream = nullptr) {
+        check(lsmb_lset_probe_dev(ls_, d_data, d_offsets, key_len, n, d_out, stream));
+    }
+
+   private:
+    static const uint8_t* u8(std::string_view s) { return reinterpret_cast<const uint8_t*>(s.data()); }
+    lsmb_lset* ls_ = nullptr;
+};
+
 }  // namespace lsm::bloom

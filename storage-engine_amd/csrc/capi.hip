@@ -17,6 +17,7 @@
 #include <vector>
 
 #include "ctx.hpp"
+#include "lset_order.hpp"
 
 using namespace lsmb;
 
@@ -1136,6 +1137,253 @@ int lsmb_fset_probe_lists(lsmb_fset* fs, const uint8_t* data, const uint64_t* of
         HIP_TRY(hipMemcpyAsync(index, fs->lindex.p, got * 4, hipMemcpyDeviceToHost, c->st));
         HIP_TRY(hipStreamSynchronize(c->st));
     }
+    return LSMB_OK;
+}
+
+// ---------------------------------------------------------------- level sets
+// An immutable, device-resident snapshot of the store's non-overlapping
+// levels (one per Version, src/db/mod.rs:255-267): rows of tables with
+// pairwise disjoint key ranges, any number per row.  Tables are added in any
+// order, each filter copied into a device arena as it arrives; seal sorts the
+// rows, checks them (lset_order.hpp) and uploads the descriptors.  A sealed
+// set is only read, so its probes need no scratch and no ordering.
+struct lsmb_lset {
+    lsmb_ctx* c = nullptr;
+    struct Table {
+        uint32_t id = 0, num_bits = 0, k = 0;
+        const uint32_t* words = nullptr;  // in the arena
+        std::vector<uint8_t> lo, hi;
+    };
+    std::vector<Table> row[kLsetMaxRows];
+    uint32_t nrows = 0;  // 1 + highest row added
+    bool sealed = false;
+    // filter words: bump-allocated from chunks that are never reallocated
+    std::vector<DevBuf> chunks;
+    size_t chunk_used = 0;
+    DevBuf bounds, desc, pfx;  // seal: the bound keys' bytes, LsetTable[], prefix pairs
+    LsetRows rows{};
+    hipStream_t ust = nullptr;  // uploads
+};
+
+namespace {
+
+constexpr size_t kLsetChunkBytes = 4u << 20;
+
+// 16-B-aligned device memory for one filter's words (a filter larger than a
+// chunk gets a chunk of its own).
+int lset_arena_alloc(lsmb_lset* ls, size_t bytes, void** out) {
+    bytes = (std::max<size_t>(bytes, 8) + 15) & ~(size_t)15;
+    if (ls->chunks.empty() || ls->chunk_used + bytes > ls->chunks.back().bytes) {
+        DevBuf b;
+        HIP_TRY(b.ensure(std::max(bytes, kLsetChunkBytes)));
+        ls->chunks.push_back(b);
+        ls->chunk_used = 0;
+    }
+    *out = (uint8_t*)ls->chunks.back().p + ls->chunk_used;
+    ls->chunk_used += bytes;
+    return LSMB_OK;
+}
+
+int lset_add_common(lsmb_lset* ls, uint32_t row, uint32_t table_id, const uint8_t* words_le, uint32_t num_bits,
+                    uint32_t k, const uint8_t* min_key, uint64_t min_len, const uint8_t* max_key, uint64_t max_len) {
+    if (int rc = check_filter(num_bits, k)) return rc;
+    if ((min_len && !min_key) || (max_len && !max_key)) return fail(LSMB_EINVAL, "null key range");
+    if (min_len > UINT32_MAX || max_len > UINT32_MAX) return fail(LSMB_EINVAL, "range key too long");
+    if (ls->row[row].size() >= UINT32_MAX) return fail(LSMB_EINVAL, "level set row %u is full", row);
+    DevGuard g(ls->c->dev);
+    const uint64_t nw = nwords64(num_bits);
+    void* dw = nullptr;
+    if (int rc = lset_arena_alloc(ls, nw * 8, &dw)) return rc;
+    if (nw) {
+        HIP_TRY(hipMemcpyAsync(dw, words_le, nw * 8, hipMemcpyHostToDevice, ls->ust));
+        HIP_TRY(hipStreamSynchronize(ls->ust));  // the caller's block is free to go
+    }
+    lsmb_lset::Table t;
+    t.id = table_id;
+    t.num_bits = num_bits;
+    t.k = k;
+    t.words = (const uint32_t*)dw;
+    t.lo.assign(min_key, min_key + min_len);
+    t.hi.assign(max_key, max_key + max_len);
+    ls->row[row].push_back(std::move(t));
+    ls->nrows = std::max(ls->nrows, row + 1);
+    return LSMB_OK;
+}
+
+int lset_add_check(const lsmb_lset* ls, uint32_t row, uint32_t table_id) {
+    if (!ls) return fail(LSMB_EINVAL, "null level set");
+    if (ls->sealed) return fail(LSMB_EINVAL, "level set is sealed: a new Version takes a new set");
+    if (row >= kLsetMaxRows) return fail(LSMB_EINVAL, "row %u: a level set has %u rows", row, kLsetMaxRows);
+    if (table_id == LSMB_LSET_NONE) return fail(LSMB_EINVAL, "table id 0xFFFFFFFF is the probe's 'no table' answer");
+    return LSMB_OK;
+}
+
+int lset_probe_check(const lsmb_lset* ls) {
+    if (!ls) return fail(LSMB_EINVAL, "null level set");
+    if (!ls->sealed) return fail(LSMB_EINVAL, "level set not sealed");
+    return LSMB_OK;
+}
+
+}  // namespace
+
+int lsmb_lset_open(lsmb_ctx* c, lsmb_lset** out) {
+    if (!c || !out) return fail(LSMB_EINVAL, "null argument");
+    *out = nullptr;
+    DevGuard g(c->dev);
+    lsmb_lset* ls = new lsmb_lset;
+    ls->c = c;
+    if (hipStreamCreateWithFlags(&ls->ust, hipStreamNonBlocking) != hipSuccess) {
+        delete ls;
+        return fail(LSMB_EHIP, "level set: stream creation failed");
+    }
+    *out = ls;
+    return LSMB_OK;
+}
+
+void lsmb_lset_close(lsmb_lset* ls) {
+    if (!ls) return;
+    {
+        DevGuard g(ls->c->dev);
+        if (ls->ust) hipStreamSynchronize(ls->ust), hipStreamDestroy(ls->ust);
+        for (auto& b : ls->chunks) b.release();
+        ls->bounds.release();
+        ls->desc.release();
+        ls->pfx.release();
+    }
+    delete ls;
+}
+
+int lsmb_lset_add(lsmb_lset* ls, uint32_t row, uint32_t table_id, const uint8_t* block, uint64_t len,
+                  const uint8_t* min_key, uint64_t min_len, const uint8_t* max_key, uint64_t max_len) {
+    if (int rc = lset_add_check(ls, row, table_id)) return rc;
+    uint32_t k, nb, nw;
+    if (int rc = lsmb_deserialize_header(block, len, &k, &nb, &nw)) return rc;
+    return lset_add_common(ls, row, table_id, block + 12, nb, k, min_key, min_len, max_key, max_len);
+}
+
+int lsmb_lset_add_words(lsmb_lset* ls, uint32_t row, uint32_t table_id, const uint64_t* words, uint32_t num_bits,
+                        uint32_t num_hashes, const uint8_t* min_key, uint64_t min_len, const uint8_t* max_key,
+                        uint64_t max_len) {
+    if (int rc = lset_add_check(ls, row, table_id)) return rc;
+    if (!words && nwords64(num_bits)) return fail(LSMB_EINVAL, "null words");
+    return lset_add_common(ls, row, table_id, (const uint8_t*)words, num_bits, num_hashes, min_key, min_len, max_key,
+                           max_len);
+}
+
+int lsmb_lset_seal(lsmb_lset* ls) {
+    if (!ls) return fail(LSMB_EINVAL, "null level set");
+    if (ls->sealed) return LSMB_OK;
+    // per row: sorted by min_key, ranges disjoint
+    std::vector<uint32_t> order[kLsetMaxRows];
+    uint64_t ntab = 0;
+    for (uint32_t r = 0; r < ls->nrows; r++) {
+        const auto& T = ls->row[r];
+        std::vector<LsetRange> rg(T.size());
+        for (size_t j = 0; j < T.size(); j++)
+            rg[j] = LsetRange{T[j].lo.data(), T[j].lo.size(), T[j].hi.data(), T[j].hi.size(), T[j].id};
+        LsetOrderError err;
+        if (!lset_order_row(rg.data(), (uint32_t)rg.size(), &order[r], &err)) {
+            if (err.inverted) return fail(LSMB_EINVAL, "level set row %u: table %u has min_key > max_key", r, err.id_a);
+            return fail(LSMB_EINVAL, "level set row %u: tables %u and %u overlap (max_key of %u >= min_key of %u)", r,
+                        err.id_a, err.id_b, err.id_a, err.id_b);
+        }
+        ntab += T.size();
+    }
+    // the bound keys' bytes, the descriptors and the search prefixes, each row's
+    // tables in sorted order, rows back to back
+    std::vector<uint8_t> blob;
+    std::vector<LsetTable> d;
+    std::vector<ulonglong2> px;
+    d.reserve(ntab);
+    px.reserve(ntab);
+    for (uint32_t r = 0; r < ls->nrows; r++)
+        for (uint32_t j : order[r]) {
+            const auto& S = ls->row[r][j];
+            LsetTable t;
+            memset(&t, 0, sizeof t);
+            t.words32 = S.words;
+            t.lo = (const uint8_t*)(uintptr_t)blob.size();  // offsets until the blob has its address
+            blob.insert(blob.end(), S.lo.begin(), S.lo.end());
+            t.hi = (const uint8_t*)(uintptr_t)blob.size();
+            blob.insert(blob.end(), S.hi.begin(), S.hi.end());
+            const HostPfx16 pl = host_prefix16(S.lo.data(), S.lo.size()), ph = host_prefix16(S.hi.data(), S.hi.size());
+            t.lo_w0 = pl.w0;
+            t.lo_w1 = pl.w1;
+            t.md = Mod32::make(S.num_bits ? S.num_bits : 1);
+            t.lo_len = (uint32_t)S.lo.size();
+            t.hi_len = (uint32_t)S.hi.size();
+            t.num_bits = S.num_bits;
+            t.k = S.k;
+            t.id = S.id;
+            d.push_back(t);
+            ulonglong2 q;
+            q.x = ph.w0;
+            q.y = ph.w1;
+            px.push_back(q);
+        }
+    DevGuard g(ls->c->dev);
+    HIP_TRY(ls->bounds.ensure(blob.size() + 16));
+    HIP_TRY(ls->desc.ensure(std::max<size_t>(d.size(), 1) * sizeof(LsetTable)));
+    HIP_TRY(ls->pfx.ensure(std::max<size_t>(px.size(), 1) * sizeof(ulonglong2)));
+    const uint8_t* base = (const uint8_t*)ls->bounds.p;
+    for (auto& t : d) {
+        t.lo = base + (uintptr_t)t.lo;
+        t.hi = base + (uintptr_t)t.hi;
+    }
+    if (!blob.empty()) HIP_TRY(hipMemcpyAsync(ls->bounds.p, blob.data(), blob.size(), hipMemcpyHostToDevice, ls->ust));
+    if (!d.empty()) {
+        HIP_TRY(hipMemcpyAsync(ls->desc.p, d.data(), d.size() * sizeof(LsetTable), hipMemcpyHostToDevice, ls->ust));
+        HIP_TRY(hipMemcpyAsync(ls->pfx.p, px.data(), px.size() * sizeof(ulonglong2), hipMemcpyHostToDevice, ls->ust));
+    }
+    HIP_TRY(hipStreamSynchronize(ls->ust));  // blob, d and px are host temporaries
+    memset(&ls->rows, 0, sizeof ls->rows);
+    ls->rows.nrows = ls->nrows;
+    uint64_t at = 0;
+    for (uint32_t r = 0; r < ls->nrows; r++) {
+        const uint32_t m = (uint32_t)ls->row[r].size();
+        if (m) {
+            ls->rows.row[r].hi_pfx = (const ulonglong2*)ls->pfx.p + at;
+            ls->rows.row[r].tab = (const LsetTable*)ls->desc.p + at;
+        }
+        ls->rows.row[r].ntab = m;
+        at += m;
+    }
+    ls->sealed = true;
+    return LSMB_OK;
+}
+
+int lsmb_lset_rows(const lsmb_lset* ls) { return ls ? (int)ls->nrows : 0; }
+
+uint64_t lsmb_lset_tables(const lsmb_lset* ls, uint32_t row) {
+    return ls && row < kLsetMaxRows ? (uint64_t)ls->row[row].size() : 0;
+}
+
+int lsmb_lset_probe_dev(lsmb_lset* ls, const void* d_data, const void* d_offsets, uint32_t key_len, uint64_t n,
+                        void* d_out, void* stream) {
+    if (int rc = lset_probe_check(ls)) return rc;
+    if (n == 0 || ls->nrows == 0) return LSMB_OK;
+    if (!d_out || !d_data) return fail(LSMB_EINVAL, "null keys or output");
+    DevGuard g(ls->c->dev);
+    KeyBatch kb{(const uint8_t*)d_data, (const uint64_t*)d_offsets, key_len, n};
+    HIP_TRY(launch_lset_probe(kb, ls->rows, (uint32_t*)d_out, ls->c->num_cus, pick_stream(ls->c, stream)));
+    return LSMB_OK;
+}
+
+int lsmb_lset_probe(lsmb_lset* ls, const uint8_t* data, const uint64_t* offsets, uint32_t key_len, uint64_t n,
+                    uint32_t* out) {
+    if (int rc = lset_probe_check(ls)) return rc;
+    if (n == 0 || ls->nrows == 0) return LSMB_OK;
+    if (!out || (!data && (offsets ? offsets[n] > offsets[0] : key_len > 0)))
+        return fail(LSMB_EINVAL, "null keys or output");
+    lsmb_ctx* c = ls->c;
+    DevGuard g(c->dev);
+    const uint64_t obytes = (uint64_t)ls->nrows * n * 4;
+    HIP_TRY(c->out.ensure(obytes));
+    KeyBatch kb;
+    if (int rc = stage_host_keys(c, data, offsets, key_len, n, &kb)) return rc;
+    HIP_TRY(launch_lset_probe(kb, ls->rows, (uint32_t*)c->out.p, c->num_cus, c->st));
+    HIP_TRY(hipMemcpyAsync(out, c->out.p, obytes, hipMemcpyDeviceToHost, c->st));
+    HIP_TRY(hipStreamSynchronize(c->st));
     return LSMB_OK;
 }
 

@@ -226,6 +226,38 @@ hipError_t launch_fset_lists(const uint8_t* d_rows, uint32_t row_bytes, uint64_t
                              uint64_t* d_starts, uint32_t* d_index, uint64_t cap, hipStream_t st,
                              hipEvent_t done = nullptr);
 
+// A level set (lsmb_lset): up to kLsetMaxRows rows (the store's levels below
+// L0), each any number of tables with pairwise disjoint key ranges, sorted by
+// min_key — so the max keys ascend too, and at most one table of a row holds a
+// given key.  hi_pfx[j] = the zero-padded 16-byte prefix of table j's max_key
+// as two big-endian words (FsetPoint's w0, w1): the array the kernel searches.
+constexpr uint32_t kLsetMaxRows = 8;
+constexpr uint32_t kLsetNone = 0xFFFFFFFFu;
+struct LsetTable {
+    const uint32_t* words32;
+    const uint8_t* lo;  // min_key, max_key: the full bytes (device memory)
+    const uint8_t* hi;
+    uint64_t lo_w0, lo_w1;  // min_key's 16-byte prefix
+    Mod32 md;
+    uint32_t lo_len, hi_len;
+    uint32_t num_bits, k;
+    uint32_t id, pad;  // the caller's table id: the answer
+};
+struct LsetRow {
+    const ulonglong2* hi_pfx;  // ntab entries (x = w0, y = w1), ascending
+    const LsetTable* tab;      // ntab, in the same order
+    uint32_t ntab, pad;
+};
+struct LsetRows {
+    LsetRow row[kLsetMaxRows];  // by value: uniform kernel arguments
+    uint32_t nrows;
+};
+
+// d_out[r * n + i] = the id of the one table t of row r with lo_t <= key i <=
+// hi_t && may_contain(filter t, key i), else kLsetNone; r < rows.nrows.  A
+// sealed set is read-only: the launch needs no scratch.
+hipError_t launch_lset_probe(const KeyBatch& kb, const LsetRows& rows, uint32_t* d_out, int num_cus, hipStream_t st);
+
 // A kernel launch whose completion also completes `done` (when non-null):
 // hipExtLaunchKernelGGL tracks the event with the dispatch's own completion
 // signal, where hipEventRecord after the launch would put a marker packet in

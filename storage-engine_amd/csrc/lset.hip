@@ -1,0 +1,117 @@
+// lset.hip — level-set probe for gfx950 (MI355X): the batched form of DB::get's
+// walk over L1 and below (src/db/mod.rs:255-267, "L1+: no overlaps, at most
+// one SSTable contains the key").  Per key and per row (level) the answer is
+// one table id or none, so a row of thousands of tables costs one binary
+// search, one range check and at most one filter walk — not a mask bit per
+// table as in a filter set (bloom_probe.hip).
+//
+// One lane per key, grid-stride.  The key is hashed once and its 16-byte
+// prefix taken once; then per row:
+//   1. a lower bound over the row's max-key prefixes (global memory: a
+//      thousand-table row does not fit LDS; the top of the search tree stays
+//      in L1/L2) for the first table whose max_key >= key;
+//   2. full compares over the tables whose prefix equals the key's (bounds or
+//      keys longer than 16 bytes sharing their first 16);
+//   3. min_key <= key;
+//   4. the table's own filter walked from L2, out at the first clear bit
+//      (src/bloom/mod.rs:88-90).
+// csrc/lset_order.hpp states steps 1-3 in plain C++ (lset_find) for the CPU
+// tests.  Output out[r * n + i]: a row's answers are contiguous, so the stores
+// of a wave coalesce.
+#include "kernels.hpp"
+#include "keyorder.hpp"
+#include "keysrc.hpp"
+
+namespace lsmb {
+namespace {
+
+using ks::Fixed16;
+using ks::FixedN;
+using ks::VarLen;
+
+// <0, 0, >0: the bound (prefix bw0:bw1, bytes bp[0..bl)) against the key.
+// Different prefixes decide; equal ones order by length when both strings fit
+// 16 bytes (they differ in trailing zero bytes at most), else by the bytes.
+__device__ __forceinline__ int bound_cmp(uint64_t bw0, uint64_t bw1, const uint8_t* bp, uint32_t bl, const Pfx16& kx,
+                                         const uint8_t* kp, uint64_t kl) {
+    if (bw0 != kx.w0) return bw0 < kx.w0 ? -1 : 1;
+    if (bw1 != kx.w1) return bw1 < kx.w1 ? -1 : 1;
+    if (bl <= 16 && kl <= 16) return bl < kl ? -1 : (bl > kl ? 1 : 0);
+    return -key_cmp(kp, kl, bp, bl);
+}
+
+template <class Src>
+__global__ __launch_bounds__(256) void k_lset_probe(Src src, uint64_t n, LsetRows rows, uint32_t* __restrict__ out) {
+    const uint64_t gs = (uint64_t)gridDim.x * blockDim.x;
+    for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gs) {
+        const H128 h = src.hash(i);
+        const uint8_t* kp = src.bytes(i);
+        const uint64_t kl = src.key_len(i);
+        const Pfx16 kx = prefix16(kp, kl);
+        for (uint32_t r = 0; r < rows.nrows; r++) {
+            const LsetRow& R = rows.row[r];
+            const uint32_t m = R.ntab;
+            // branch-free lower bound: a uniform loop of ceil(log2(m + 1)) steps
+            uint32_t lo = 0;
+            for (uint32_t step = m ? 1u << (31 - __builtin_clz(m)) : 0u; step; step >>= 1) {
+                const uint32_t j = lo + step - 1;
+                if (j < m) {
+                    const ulonglong2 q = R.hi_pfx[j];
+                    if (q.x < kx.w0 || (q.x == kx.w0 && q.y < kx.w1)) lo += step;
+                }
+            }
+            while (lo < m) {
+                const ulonglong2 q = R.hi_pfx[lo];
+                if (q.x != kx.w0 || q.y != kx.w1) break;  // max_key's prefix above the key's: max_key > key
+                const LsetTable& T = R.tab[lo];
+                if (bound_cmp(q.x, q.y, T.hi, T.hi_len, kx, kp, kl) >= 0) break;
+                lo++;
+            }
+            uint32_t ans = kLsetNone;
+            if (lo < m) {
+                const LsetTable& T = R.tab[lo];
+                if (bound_cmp(T.lo_w0, T.lo_w1, T.lo, T.lo_len, kx, kp, kl) <= 0) {
+                    bool hit = true;
+                    const uint32_t k = T.k;
+                    if (k) {
+                        const Mod32 md = T.md;
+                        const uint32_t* __restrict__ w = T.words32;
+                        PosWalk pw(md, h.lo, h.hi);
+                        for (uint32_t j = 0; j < k; j++) {
+                            const uint32_t p = pw.pos();
+                            if (!((w[p >> 5] >> (p & 31)) & 1u)) {
+                                hit = false;
+                                break;
+                            }
+                            pw.next(md);
+                        }
+                    }
+                    if (hit) ans = T.id;
+                }
+            }
+            out[(uint64_t)r * n + i] = ans;
+        }
+    }
+}
+
+template <class Src>
+hipError_t lset_probe_with(const Src& src, uint64_t n, const LsetRows& rows, uint32_t* out, int num_cus, hipStream_t st) {
+    uint64_t g = (n + 255) / 256;
+    const uint64_t gmax = (uint64_t)num_cus * 8;
+    if (g > gmax) g = gmax;
+    k_lset_probe<Src><<<dim3((uint32_t)g), dim3(256), 0, st>>>(src, n, rows, out);
+    return hipGetLastError();
+}
+
+}  // namespace
+
+hipError_t launch_lset_probe(const KeyBatch& kb, const LsetRows& rows, uint32_t* d_out, int num_cus, hipStream_t st) {
+    if (kb.n == 0 || rows.nrows == 0) return hipSuccess;
+    if (rows.nrows > kLsetMaxRows) return hipErrorInvalidValue;
+    if (kb.offsets) return lset_probe_with(VarLen{kb.data, kb.offsets}, kb.n, rows, d_out, num_cus, st);
+    if (kb.key_len == 16 && (reinterpret_cast<uintptr_t>(kb.data) & 15) == 0)
+        return lset_probe_with(Fixed16{reinterpret_cast<const uint4*>(kb.data)}, kb.n, rows, d_out, num_cus, st);
+    return lset_probe_with(FixedN{kb.data, kb.key_len}, kb.n, rows, d_out, num_cus, st);
+}
+
+}  // namespace lsmb

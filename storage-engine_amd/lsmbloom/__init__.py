@@ -30,6 +30,8 @@ LSMB_ENODEV = -2
 LSMB_EHIP = -3
 LSMB_ECORRUPT = -4
 LSMB_ENOMEM = -5
+LSMB_LSET_MAX_LEVELS = 8
+LSMB_LSET_NONE = 0xFFFFFFFF  # LevelSet.probe: no table of this row
 
 u8p = ctypes.POINTER(ctypes.c_uint8)
 u32p = ctypes.POINTER(ctypes.c_uint32)
@@ -94,6 +96,17 @@ SIGNATURES = {
                                                  vp]),
     "lsmb_fset_probe_lists": (ctypes.c_int, [vp, u8p, u64p, ctypes.c_uint32, ctypes.c_uint64, u64p, u32p,
                                              ctypes.c_uint64]),
+    "lsmb_lset_open": (ctypes.c_int, [vp, ctypes.POINTER(vp)]),
+    "lsmb_lset_close": (None, [vp]),
+    "lsmb_lset_add": (ctypes.c_int, [vp, ctypes.c_uint32, ctypes.c_uint32, u8p, ctypes.c_uint64, u8p, ctypes.c_uint64,
+                                     u8p, ctypes.c_uint64]),
+    "lsmb_lset_add_words": (ctypes.c_int, [vp, ctypes.c_uint32, ctypes.c_uint32, u64p, ctypes.c_uint32, ctypes.c_uint32,
+                                           u8p, ctypes.c_uint64, u8p, ctypes.c_uint64]),
+    "lsmb_lset_seal": (ctypes.c_int, [vp]),
+    "lsmb_lset_rows": (ctypes.c_int, [vp]),
+    "lsmb_lset_tables": (ctypes.c_uint64, [vp, ctypes.c_uint32]),
+    "lsmb_lset_probe": (ctypes.c_int, [vp, u8p, u64p, ctypes.c_uint32, ctypes.c_uint64, u32p]),
+    "lsmb_lset_probe_dev": (ctypes.c_int, [vp, vp, vp, ctypes.c_uint32, ctypes.c_uint64, vp, vp]),
     "lsmb_build_strategy": (ctypes.c_char_p, [ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint64]),
     "lsmb_host_max_keys": (ctypes.c_uint64, []),
     "lsmb_build_sweeps": (ctypes.c_int, [ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint64]),
@@ -660,6 +673,90 @@ class FilterSet:
         cap = int(index.numel()) if index is not None else 0
         _check(lib().lsmb_fset_probe_lists_dev(self.h, vp(data.data_ptr()), offs, key_len, n, vp(starts.data_ptr()),
                                                vp(index.data_ptr()) if cap else None, cap, Context._stream(stream)))
+
+
+class LevelSet:
+    """Device-resident snapshot of the store's non-overlapping levels (lsmb_lset),
+    one per Version: rows of tables with pairwise disjoint key ranges, any
+    number per row.  add / add_filter in any order, then seal(), then probe:
+
+    probe(keys)[r, i] = table_id of the one table t of row r with
+    min_t <= key_i <= max_t and may_contain(filter t, key_i), else LSMB_LSET_NONE.
+    """
+
+    def __init__(self, ctx=None):
+        self.ctx = ctx or default_context()
+        h = vp()
+        _check(lib().lsmb_lset_open(self.ctx.h, ctypes.byref(h)))
+        self.h = h
+
+    def close(self):
+        if self.h:
+            lib().lsmb_lset_close(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def add(self, row, table_id, block, min_key, max_key):
+        """block: serialized filter bytes (BloomFilter::serialize)."""
+        b, n = _key(block)
+        lo, nlo = _key(min_key)
+        hi, nhi = _key(max_key)
+        _check(lib().lsmb_lset_add(self.h, int(row), int(table_id), _p(b, u8p), n, _p(lo, u8p), nlo, _p(hi, u8p), nhi))
+
+    def add_filter(self, row, table_id, filt, min_key, max_key):
+        """filt: BloomFilter."""
+        w = np.ascontiguousarray(filt.bits, dtype=np.uint64)
+        if w.size == 0:
+            w = np.zeros(1, np.uint64)
+        lo, nlo = _key(min_key)
+        hi, nhi = _key(max_key)
+        _check(lib().lsmb_lset_add_words(self.h, int(row), int(table_id), _p(w, u64p), filt.num_bits(),
+                                         filt.num_hashes(), _p(lo, u8p), nlo, _p(hi, u8p), nhi))
+
+    def seal(self):
+        _check(lib().lsmb_lset_seal(self.h))
+
+    def rows(self):
+        return int(lib().lsmb_lset_rows(self.h))
+
+    def tables(self, row):
+        return int(lib().lsmb_lset_tables(self.h, int(row)))
+
+    def probe(self, data, offsets=None, key_len=0):
+        """Packed host keys (as Context.probe) -> uint32 table ids, shape (rows(), n)."""
+        data = np.ascontiguousarray(data, dtype=np.uint8).reshape(-1)
+        if offsets is not None:
+            offsets = np.ascontiguousarray(offsets, dtype=np.uint64)
+            n = offsets.size - 1
+            op = _p(offsets, u64p)
+        else:
+            n = data.size // key_len if key_len else 0
+            op = None
+        out = np.empty((self.rows(), n), dtype=np.uint32)
+        if data.size == 0:
+            data = np.zeros(1, np.uint8)
+        _check(lib().lsmb_lset_probe(self.h, _p(data, u8p), op, key_len, n,
+                                     _p(out if out.size else np.zeros(1, np.uint32), u32p)))
+        return out
+
+    def probe_keys(self, keys):
+        """list of bytes -> uint32 table ids, shape (rows(), len(keys))."""
+        lens = np.array([len(k) for k in keys], dtype=np.uint64)
+        offs = np.zeros(len(keys) + 1, dtype=np.uint64)
+        np.cumsum(lens, out=offs[1:])
+        return self.probe(np.frombuffer(b"".join(bytes(k) for k in keys), dtype=np.uint8), offs)
+
+    def probe_dev(self, data, n, out, offsets=None, key_len=0, stream=None):
+        """Device keys -> device table ids (lsmb_lset_probe_dev): out an int32 /
+        uint32 tensor of rows() * n, row r's answers at out[r * n : (r + 1) * n]."""
+        offs = vp(offsets.data_ptr()) if offsets is not None else None
+        _check(lib().lsmb_lset_probe_dev(self.h, vp(data.data_ptr()), offs, key_len, n, vp(out.data_ptr()),
+                                         Context._stream(stream)))
 
 
 def build_strategy(num_bits, n, k=7):
