@@ -546,6 +546,61 @@ int lsmb_lset_probe(lsmb_lset* ls, const uint8_t* data, const uint64_t* offsets,
 int lsmb_lset_probe_dev(lsmb_lset* ls, const void* d_data, const void* d_offsets, uint32_t key_len, uint64_t n,
                         void* d_out, void* stream);
 
+/* ---- a level set's answer per table ---------------------------------------- */
+/* What a reader that works table by table wants from the levels below L0
+ * (src/db/mod.rs:255-267 picks the one table per level, src/sstable/reader.rs:
+ * 192-199 is the range-and-bloom check each list entry has passed): open
+ * table g, look up the keys that may be in it, close it.  Table ids are the
+ * caller's and need not be unique, so the lists are keyed by ORDINAL: with R =
+ * lsmb_lset_rows(ls), T_r = lsmb_lset_tables(ls, r) and base_r = T_0 + ... +
+ * T_{r-1}, table j of row r in the row's sealed order (ascending min_key) has
+ * the ordinal g = base_r + j, and G = base_R tables have one. */
+
+/* G (src/db/mod.rs:255-267, src/sstable/reader.rs:192-199: every table a get
+ * may consult below L0).  0 for NULL or an unsealed set. */
+uint64_t lsmb_lset_total_tables(const lsmb_lset* ls);
+
+/* Host outputs: ids[G] = the table id of every ordinal, row_base[R + 1] =
+ * base_0 .. base_R (the tables of src/db/mod.rs:255-267's levels in the order
+ * src/sstable/reader.rs:192-199's min_key sorts them).  Either pointer may be
+ * NULL.  Before seal: LSMB_EINVAL. */
+int lsmb_lset_table_order(const lsmb_lset* ls, uint32_t* ids, uint64_t* row_base);
+
+/* Bytes of device workspace a lists probe of n keys needs (the batched walk of
+ * src/db/mod.rs:255-267 with src/sstable/reader.rs:192-199's checks keeps its
+ * intermediate answers there).  0 for NULL, an unsealed set, n == 0, an empty
+ * set or n > 2^32-1. */
+uint64_t lsmb_lset_lists_work_bytes(const lsmb_lset* ls, uint64_t n);
+
+/* d_starts is uint64_t[G + 1], d_index is uint32_t[cap].  For every ordinal g,
+ * d_index[d_starts[g] .. d_starts[g+1]) = the indices i, ascending, of the
+ * keys for which lsmb_lset_probe answers table g in g's row:
+ *     min_g <= key i <= max_g && may_contain(filter g, key i)
+ * (src/db/mod.rs:255-267, src/sstable/reader.rs:192-199).  d_starts[0] = 0,
+ * d_starts[G] = the total number of entries.  d_starts is always exact; the
+ * entry at global position p is written iff p < cap, nothing else in d_index
+ * is touched (cap == 0 with a null d_index is a counting call), as
+ * lsmb_fset_probe_lists_dev.  n == 0 or G == 0 writes G + 1 zero starts and
+ * nothing else.  LSMB_EINVAL: n > 2^32-1, work_bytes below
+ * lsmb_lset_lists_work_bytes(ls, n), a null (or not 16-byte-aligned) d_work
+ * with n > 0 && G > 0, a call before seal; the outputs are then untouched.
+ * Asynchronous on `stream`, no host synchronisation inside.  The sealed set
+ * stays read-only: ALL scratch is the caller's d_work, so lists probes on
+ * different streams with different workspaces need no ordering among
+ * themselves (two probes sharing one workspace do).  The same keys give the
+ * same bytes in d_starts and d_index on every run. */
+int lsmb_lset_probe_lists_dev(lsmb_lset* ls, const void* d_data, const void* d_offsets, uint32_t key_len, uint64_t n,
+                              void* d_starts, void* d_index, uint64_t cap, void* d_work, uint64_t work_bytes,
+                              void* stream);
+
+/* Host keys and host outputs (starts[G + 1], index[cap]); synchronous; the
+ * lists of src/db/mod.rs:255-267's levels under src/sstable/reader.rs:192-199's
+ * checks as above.  The workspace is the context's own scratch, so calls on
+ * one context run one at a time, as its other host entry points.  Only starts
+ * and min(total, cap) entries cross PCIe on the way back. */
+int lsmb_lset_probe_lists(lsmb_lset* ls, const uint8_t* data, const uint64_t* offsets, uint32_t key_len, uint64_t n,
+                          uint64_t* starts, uint32_t* index, uint64_t cap);
+
 /* ---- introspection ------------------------------------------------------- */
 
 /* Name of the device build strategy the dispatcher picks for (num_bits, k, n):

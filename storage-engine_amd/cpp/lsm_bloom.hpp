@@ -301,6 +301,53 @@ class LevelSet {
         check(lsmb_lset_probe_dev(ls_, d_data, d_offsets, key_len, n, d_out, stream));
     }
 
+    // The answer per table (lsmb_lset_probe_lists), keyed by ordinal: table j
+    // of row r in the row's sealed order (ascending min_key) is ordinal
+    // row_base[r] + j, ids[g] its table id.
+    uint64_t total_tables() const { return lsmb_lset_total_tables(ls_); }
+    struct TableOrder {
+        std::vector<uint32_t> ids;       // total_tables()
+        std::vector<uint64_t> row_base;  // rows() + 1
+    };
+    TableOrder table_order() const {
+        TableOrder o;
+        o.ids.resize(total_tables());
+        o.row_base.resize(static_cast<size_t>(rows()) + 1);
+        check(lsmb_lset_table_order(ls_, o.ids.data(), o.row_base.data()));
+        return o;
+    }
+    // index[starts[g] .. starts[g+1]) = the ascending indices of the keys for
+    // which probe() answers table g in g's row; starts has total_tables() + 1
+    // entries.  A counting call sizes the index.
+    struct Lists {
+        std::vector<uint64_t> starts;
+        std::vector<uint32_t> index;
+    };
+    Lists probe_lists(const std::vector<std::string>& keys) {
+        std::vector<uint64_t> offs(keys.size() + 1, 0);
+        std::string data;
+        for (size_t i = 0; i < keys.size(); i++) {
+            data += keys[i];
+            offs[i + 1] = data.size();
+        }
+        Lists out;
+        out.starts.assign(total_tables() + 1, 0);
+        check(lsmb_lset_probe_lists(ls_, u8(data), offs.data(), 0, keys.size(), out.starts.data(), nullptr, 0));
+        out.index.resize(out.starts.back());
+        if (!out.index.empty())
+            check(lsmb_lset_probe_lists(ls_, u8(data), offs.data(), 0, keys.size(), out.starts.data(), out.index.data(),
+                                        out.index.size()));
+        return out;
+    }
+    // Device keys, outputs (d_starts: total_tables() + 1 uint64_t, d_index: cap
+    // uint32_t) and workspace (lists_work_bytes(n) bytes), asynchronous on `stream`.
+    uint64_t lists_work_bytes(uint64_t n) const { return lsmb_lset_lists_work_bytes(ls_, n); }
+    void probe_lists_dev(const void* d_data, const void* d_offsets, uint32_t key_len, uint64_t n, void* d_starts,
+                         void* d_index, uint64_t cap, void* d_work, uint64_t work_bytes, void* stream = nullptr) {
+        check(lsmb_lset_probe_lists_dev(ls_, d_data, d_offsets, key_len, n, d_starts, d_index, cap, d_work, work_bytes,
+                                        stream));
+    }
+
    private:
     static const uint8_t* u8(std::string_view s) { return reinterpret_cast<const uint8_t*>(s.data()); }
     lsmb_lset* ls_ = nullptr;

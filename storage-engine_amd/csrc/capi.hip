@@ -17,6 +17,7 @@
 #include <vector>
 
 #include "ctx.hpp"
+#include "lset_lists_plan.hpp"
 #include "lset_order.hpp"
 
 using namespace lsmb;
@@ -1162,6 +1163,10 @@ struct lsmb_lset {
     size_t chunk_used = 0;
     DevBuf bounds, desc, pfx;  // seal: the bound keys' bytes, LsetTable[], prefix pairs
     LsetRows rows{};
+    // seal: the table id of every ordinal (row by row, each in its sealed
+    // order) and the first ordinal of every row, base[nrows] = all tables
+    std::vector<uint32_t> ids;
+    uint64_t base[kLsetMaxRows + 1] = {0};
     hipStream_t ust = nullptr;  // uploads
 };
 
@@ -1346,8 +1351,12 @@ int lsmb_lset_seal(lsmb_lset* ls) {
             ls->rows.row[r].tab = (const LsetTable*)ls->desc.p + at;
         }
         ls->rows.row[r].ntab = m;
+        ls->base[r] = at;
         at += m;
     }
+    for (uint32_t r = ls->nrows; r <= kLsetMaxRows; r++) ls->base[r] = at;
+    ls->ids.resize(d.size());
+    for (size_t g = 0; g < d.size(); g++) ls->ids[g] = d[g].id;
     ls->sealed = true;
     return LSMB_OK;
 }
@@ -1384,6 +1393,86 @@ int lsmb_lset_probe(lsmb_lset* ls, const uint8_t* data, const uint64_t* offsets,
     HIP_TRY(launch_lset_probe(kb, ls->rows, (uint32_t*)c->out.p, c->num_cus, c->st));
     HIP_TRY(hipMemcpyAsync(out, c->out.p, obytes, hipMemcpyDeviceToHost, c->st));
     HIP_TRY(hipStreamSynchronize(c->st));
+    return LSMB_OK;
+}
+
+uint64_t lsmb_lset_total_tables(const lsmb_lset* ls) { return ls && ls->sealed ? ls->base[ls->nrows] : 0; }
+
+int lsmb_lset_table_order(const lsmb_lset* ls, uint32_t* ids, uint64_t* row_base) {
+    if (int rc = lset_probe_check(ls)) return rc;
+    if (ids && !ls->ids.empty()) memcpy(ids, ls->ids.data(), ls->ids.size() * sizeof(uint32_t));
+    if (row_base) memcpy(row_base, ls->base, ((size_t)ls->nrows + 1) * sizeof(uint64_t));
+    return LSMB_OK;
+}
+
+uint64_t lsmb_lset_lists_work_bytes(const lsmb_lset* ls, uint64_t n) {
+    if (!ls || !ls->sealed || n > UINT32_MAX) return 0;
+    return lset_lists_plan(n, ls->nrows, ls->base[ls->nrows]).work_bytes;
+}
+
+// The argument checks shared by both lists entry points; G = all tables.
+static int lset_lists_check(const lsmb_lset* ls, uint64_t n, const void* starts, const void* index, uint64_t cap) {
+    if (int rc = lset_probe_check(ls)) return rc;
+    if (n > UINT32_MAX) return fail(LSMB_EINVAL, "more than 2^32-1 keys (the lists hold 32-bit indices)");
+    if (ls->base[ls->nrows] > UINT32_MAX) return fail(LSMB_EINVAL, "more than 2^32-1 tables");
+    if (!starts || (cap && !index)) return fail(LSMB_EINVAL, "null output");
+    return LSMB_OK;
+}
+
+int lsmb_lset_probe_lists_dev(lsmb_lset* ls, const void* d_data, const void* d_offsets, uint32_t key_len, uint64_t n,
+                              void* d_starts, void* d_index, uint64_t cap, void* d_work, uint64_t work_bytes,
+                              void* stream) {
+    if (int rc = lset_lists_check(ls, n, d_starts, d_index, cap)) return rc;
+    const uint64_t G = ls->base[ls->nrows];
+    if (n && G) {
+        if (!d_data) return fail(LSMB_EINVAL, "null keys");
+        if (!d_work || (reinterpret_cast<uintptr_t>(d_work) & 15))
+            return fail(LSMB_EINVAL, "null or misaligned workspace (16-byte alignment)");
+        const uint64_t need = lset_lists_plan(n, ls->nrows, G).work_bytes;
+        if (work_bytes < need)
+            return fail(LSMB_EINVAL, "workspace of %llu bytes, lsmb_lset_lists_work_bytes asks for %llu",
+                        (unsigned long long)work_bytes, (unsigned long long)need);
+    }
+    DevGuard g(ls->c->dev);
+    const hipStream_t st = pick_stream(ls->c, stream);
+    if (n == 0 || G == 0) {
+        HIP_TRY(hipMemsetAsync(d_starts, 0, (G + 1) * 8, st));
+        return LSMB_OK;
+    }
+    KeyBatch kb{(const uint8_t*)d_data, (const uint64_t*)d_offsets, key_len, n};
+    HIP_TRY(launch_lset_lists(kb, ls->rows, G, (uint64_t*)d_starts, (uint32_t*)d_index, cap, d_work, work_bytes,
+                              ls->c->num_cus, st));
+    return LSMB_OK;
+}
+
+int lsmb_lset_probe_lists(lsmb_lset* ls, const uint8_t* data, const uint64_t* offsets, uint32_t key_len, uint64_t n,
+                          uint64_t* starts, uint32_t* index, uint64_t cap) {
+    if (int rc = lset_lists_check(ls, n, starts, index, cap)) return rc;
+    if (n && !data && (offsets ? offsets[n] > offsets[0] : key_len > 0)) return fail(LSMB_EINVAL, "null keys");
+    const uint64_t G = ls->base[ls->nrows];
+    memset(starts, 0, (G + 1) * 8);
+    if (n == 0 || G == 0) return LSMB_OK;
+    lsmb_ctx* c = ls->c;
+    DevGuard g(c->dev);
+    // the context's output scratch, carved: workspace | starts | index (no
+    // list entry beyond one per row and key)
+    const LsetListsPlan pl = lset_lists_plan(n, ls->nrows, G);
+    const uint64_t dcap = std::min<uint64_t>(cap, pl.pairs);
+    const uint64_t sbytes = ((G + 1) * 8 + kLlAlign - 1) / kLlAlign * kLlAlign;
+    HIP_TRY(c->out.ensure(pl.work_bytes + sbytes + std::max<uint64_t>(dcap, 1) * 4));
+    uint8_t* w = (uint8_t*)c->out.p;
+    uint64_t* d_starts = (uint64_t*)(w + pl.work_bytes);
+    uint32_t* d_index = (uint32_t*)(w + pl.work_bytes + sbytes);
+    KeyBatch kb;
+    if (int rc = stage_host_keys(c, data, offsets, key_len, n, &kb)) return rc;
+    HIP_TRY(launch_lset_lists(kb, ls->rows, G, d_starts, d_index, dcap, w, pl.work_bytes, c->num_cus, c->st));
+    HIP_TRY(hipMemcpyAsync(starts, d_starts, (G + 1) * 8, hipMemcpyDeviceToHost, c->st));
+    HIP_TRY(hipStreamSynchronize(c->st));
+    const uint64_t got = std::min<uint64_t>(starts[G], dcap);
+    if (got) {
+        HIP_TRY(hipMemcpyAsync(index, d_index, got * 4, hipMemcpyDeviceToHost, c->st));
+        HIP_TRY(hipStreamSynchronize(c->st));
+    }
     return LSMB_OK;
 }
 

@@ -258,6 +258,23 @@ struct LsetRows {
 // sealed set is read-only: the launch needs no scratch.
 hipError_t launch_lset_probe(const KeyBatch& kb, const LsetRows& rows, uint32_t* d_out, int num_cus, hipStream_t st);
 
+// The same walk answering by ordinal: d_out[r * stride + i] = (the tables of
+// rows 0 .. r-1) + the hit's place in row r's sealed order, else kLsetNone;
+// stride >= kb.n.  Ids are the caller's and need not be unique; ordinals are.
+hipError_t launch_lset_probe_ordinals(const KeyBatch& kb, const LsetRows& rows, uint32_t* d_out, uint64_t stride,
+                                      int num_cus, hipStream_t st);
+
+// The level set's answer per table (lset_lists.hip): with G = the tables of
+// all rows, for every ordinal g < G, d_index[d_starts[g] .. d_starts[g+1]) =
+// the ascending key indices i whose row answers table g; d_starts[G + 1] is
+// always exact, the entry at position p is stored iff p < cap.  All scratch is
+// d_work (16-B aligned, at least lset_lists_plan(kb.n, rows.nrows, G)
+// .work_bytes, see lset_lists_plan.hpp): the set is only read.  1 <= kb.n <=
+// 2^32-1, 1 <= G <= 2^32-1.  No host synchronisation.
+hipError_t launch_lset_lists(const KeyBatch& kb, const LsetRows& rows, uint64_t G, uint64_t* d_starts,
+                             uint32_t* d_index, uint64_t cap, void* d_work, uint64_t work_bytes, int num_cus,
+                             hipStream_t st);
+
 // A kernel launch whose completion also completes `done` (when non-null):
 // hipExtLaunchKernelGGL tracks the event with the dispatch's own completion
 // signal, where hipEventRecord after the launch would put a marker packet in

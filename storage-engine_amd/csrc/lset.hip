@@ -17,7 +17,8 @@
 //      (src/bloom/mod.rs:88-90).
 // csrc/lset_order.hpp states steps 1-3 in plain C++ (lset_find) for the CPU
 // tests.  Output out[r * n + i]: a row's answers are contiguous, so the stores
-// of a wave coalesce.
+// of a wave coalesce.  The lists probe (lset_lists.hip) runs the same walk
+// and takes the hit's ordinal instead of its id, rows a padded stride apart.
 #include "kernels.hpp"
 #include "keyorder.hpp"
 #include "keysrc.hpp"
@@ -40,14 +41,21 @@ __device__ __forceinline__ int bound_cmp(uint64_t bw0, uint64_t bw1, const uint8
     return -key_cmp(kp, kl, bp, bl);
 }
 
-template <class Src>
-__global__ __launch_bounds__(256) void k_lset_probe(Src src, uint64_t n, LsetRows rows, uint32_t* __restrict__ out) {
-    const uint64_t gs = (uint64_t)gridDim.x * blockDim.x;
+// The walk of one key batch over every row, shared by both forms of the
+// answer: kOrdinal = false stores the hit's table id at out[r * n + i];
+// kOrdinal = true its ordinal (the tables of rows 0 .. r-1, then its place in
+// row r's sealed order) at out[r * stride + i], for the lists probe
+// (lset_lists.hip).
+template <class Src, bool kOrdinal>
+__device__ __forceinline__ void lset_probe_body(const Src& src, uint64_t n, const LsetRows& rows,
+                                                uint32_t* __restrict__ out, uint64_t stride_arg, uint64_t gs) {
+    const uint64_t stride = kOrdinal ? stride_arg : n;
     for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gs) {
         const H128 h = src.hash(i);
         const uint8_t* kp = src.bytes(i);
         const uint64_t kl = src.key_len(i);
         const Pfx16 kx = prefix16(kp, kl);
+        uint32_t base = 0;  // ordinal of the row's first table
         for (uint32_t r = 0; r < rows.nrows; r++) {
             const LsetRow& R = rows.row[r];
             const uint32_t m = R.ntab;
@@ -86,12 +94,26 @@ __global__ __launch_bounds__(256) void k_lset_probe(Src src, uint64_t n, LsetRow
                             pw.next(md);
                         }
                     }
-                    if (hit) ans = T.id;
+                    if (hit) ans = kOrdinal ? base + lo : T.id;
                 }
             }
-            out[(uint64_t)r * n + i] = ans;
+            out[(uint64_t)r * stride + i] = ans;
+            base += m;
         }
     }
+}
+
+template <class Src>
+__global__ __launch_bounds__(256) void k_lset_probe(Src src, uint64_t n, LsetRows rows, uint32_t* __restrict__ out) {
+    const uint64_t gs = (uint64_t)gridDim.x * blockDim.x;
+    lset_probe_body<Src, false>(src, n, rows, out, n, gs);
+}
+
+template <class Src>
+__global__ __launch_bounds__(256) void k_lset_probe_ord(Src src, uint64_t n, LsetRows rows, uint32_t* __restrict__ out,
+                                                        uint64_t stride) {
+    const uint64_t gs = (uint64_t)gridDim.x * blockDim.x;
+    lset_probe_body<Src, true>(src, n, rows, out, stride, gs);
 }
 
 template <class Src>
@@ -100,6 +122,16 @@ hipError_t lset_probe_with(const Src& src, uint64_t n, const LsetRows& rows, uin
     const uint64_t gmax = (uint64_t)num_cus * 8;
     if (g > gmax) g = gmax;
     k_lset_probe<Src><<<dim3((uint32_t)g), dim3(256), 0, st>>>(src, n, rows, out);
+    return hipGetLastError();
+}
+
+template <class Src>
+hipError_t lset_probe_ord_with(const Src& src, uint64_t n, const LsetRows& rows, uint32_t* out, uint64_t stride,
+                               int num_cus, hipStream_t st) {
+    uint64_t g = (n + 255) / 256;
+    const uint64_t gmax = (uint64_t)num_cus * 8;
+    if (g > gmax) g = gmax;
+    k_lset_probe_ord<Src><<<dim3((uint32_t)g), dim3(256), 0, st>>>(src, n, rows, out, stride);
     return hipGetLastError();
 }
 
@@ -112,6 +144,17 @@ hipError_t launch_lset_probe(const KeyBatch& kb, const LsetRows& rows, uint32_t*
     if (kb.key_len == 16 && (reinterpret_cast<uintptr_t>(kb.data) & 15) == 0)
         return lset_probe_with(Fixed16{reinterpret_cast<const uint4*>(kb.data)}, kb.n, rows, d_out, num_cus, st);
     return lset_probe_with(FixedN{kb.data, kb.key_len}, kb.n, rows, d_out, num_cus, st);
+}
+
+hipError_t launch_lset_probe_ordinals(const KeyBatch& kb, const LsetRows& rows, uint32_t* d_out, uint64_t stride,
+                                      int num_cus, hipStream_t st) {
+    if (kb.n == 0 || rows.nrows == 0) return hipSuccess;
+    if (rows.nrows > kLsetMaxRows || stride < kb.n) return hipErrorInvalidValue;
+    if (kb.offsets) return lset_probe_ord_with(VarLen{kb.data, kb.offsets}, kb.n, rows, d_out, stride, num_cus, st);
+    if (kb.key_len == 16 && (reinterpret_cast<uintptr_t>(kb.data) & 15) == 0)
+        return lset_probe_ord_with(Fixed16{reinterpret_cast<const uint4*>(kb.data)}, kb.n, rows, d_out, stride, num_cus,
+                                   st);
+    return lset_probe_ord_with(FixedN{kb.data, kb.key_len}, kb.n, rows, d_out, stride, num_cus, st);
 }
 
 }  // namespace lsmb

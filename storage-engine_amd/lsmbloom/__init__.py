@@ -107,6 +107,13 @@ SIGNATURES = {
     "lsmb_lset_tables": (ctypes.c_uint64, [vp, ctypes.c_uint32]),
     "lsmb_lset_probe": (ctypes.c_int, [vp, u8p, u64p, ctypes.c_uint32, ctypes.c_uint64, u32p]),
     "lsmb_lset_probe_dev": (ctypes.c_int, [vp, vp, vp, ctypes.c_uint32, ctypes.c_uint64, vp, vp]),
+    "lsmb_lset_total_tables": (ctypes.c_uint64, [vp]),
+    "lsmb_lset_table_order": (ctypes.c_int, [vp, u32p, u64p]),
+    "lsmb_lset_lists_work_bytes": (ctypes.c_uint64, [vp, ctypes.c_uint64]),
+    "lsmb_lset_probe_lists_dev": (ctypes.c_int, [vp, vp, vp, ctypes.c_uint32, ctypes.c_uint64, vp, vp, ctypes.c_uint64,
+                                                 vp, ctypes.c_uint64, vp]),
+    "lsmb_lset_probe_lists": (ctypes.c_int, [vp, u8p, u64p, ctypes.c_uint32, ctypes.c_uint64, u64p, u32p,
+                                             ctypes.c_uint64]),
     "lsmb_build_strategy": (ctypes.c_char_p, [ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint64]),
     "lsmb_host_max_keys": (ctypes.c_uint64, []),
     "lsmb_build_sweeps": (ctypes.c_int, [ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint64]),
@@ -757,6 +764,72 @@ class LevelSet:
         offs = vp(offsets.data_ptr()) if offsets is not None else None
         _check(lib().lsmb_lset_probe_dev(self.h, vp(data.data_ptr()), offs, key_len, n, vp(out.data_ptr()),
                                          Context._stream(stream)))
+
+    def total_tables(self):
+        """Tables of all rows (0 before seal): the lists' ordinals are 0 .. total_tables() - 1."""
+        return int(lib().lsmb_lset_total_tables(self.h))
+
+    def table_order(self):
+        """-> (ids uint32[G], row_base uint64[rows() + 1]): table j of row r in
+        the row's sealed order (ascending min_key) has the ordinal
+        row_base[r] + j and the table id ids[row_base[r] + j]."""
+        ids = np.zeros(max(self.total_tables(), 1), dtype=np.uint32)
+        base = np.zeros(self.rows() + 1, dtype=np.uint64)
+        _check(lib().lsmb_lset_table_order(self.h, _p(ids, u32p), _p(base, u64p)))
+        return ids[:self.total_tables()], base
+
+    def lists_work_bytes(self, n):
+        """Bytes of device workspace probe_lists_dev needs for n keys."""
+        return int(lib().lsmb_lset_lists_work_bytes(self.h, int(n)))
+
+    def probe_lists(self, data, offsets=None, key_len=0, cap=None):
+        """Packed host keys (as probe) -> (starts uint64[G + 1], index
+        uint32[min(total, cap)]): index[starts[g]:starts[g+1]] = the ascending
+        indices of the keys for which probe() answers the table of ordinal g
+        (table_order()) in g's row (lsmb_lset_probe_lists).  cap=None sizes
+        index from a counting call."""
+        data = np.ascontiguousarray(data, dtype=np.uint8).reshape(-1)
+        if offsets is not None:
+            offsets = np.ascontiguousarray(offsets, dtype=np.uint64)
+            n = offsets.size - 1
+            op = _p(offsets, u64p)
+        else:
+            n = data.size // key_len if key_len else 0
+            op = None
+        if data.size == 0:
+            data = np.zeros(1, np.uint8)
+        starts = np.zeros(self.total_tables() + 1, dtype=np.uint64)
+        if cap is None:
+            _check(lib().lsmb_lset_probe_lists(self.h, _p(data, u8p), op, key_len, n, _p(starts, u64p), None, 0))
+            cap = int(starts[-1])
+            if cap == 0:
+                return starts, np.zeros(0, dtype=np.uint32)
+        cap = int(cap)
+        index = np.empty(max(cap, 1), dtype=np.uint32)
+        _check(lib().lsmb_lset_probe_lists(self.h, _p(data, u8p), op, key_len, n, _p(starts, u64p),
+                                           _p(index, u32p) if cap else None, cap))
+        return starts, index[:min(int(starts[-1]), cap)]
+
+    def probe_lists_keys(self, keys):
+        """list of bytes -> (starts, index) as probe_lists."""
+        lens = np.array([len(k) for k in keys], dtype=np.uint64)
+        offs = np.zeros(len(keys) + 1, dtype=np.uint64)
+        np.cumsum(lens, out=offs[1:])
+        return self.probe_lists(np.frombuffer(b"".join(bytes(k) for k in keys), dtype=np.uint8), offs)
+
+    def probe_lists_dev(self, data, n, starts, index, work, offsets=None, key_len=0, stream=None):
+        """Device keys -> device lists (lsmb_lset_probe_lists_dev): starts an
+        int64 / uint64 tensor of total_tables() + 1, index an int32 / uint32
+        tensor whose length is the capacity (None: a counting call), work a
+        uint8 tensor of at least lists_work_bytes(n) bytes — the probe's only
+        scratch, so probes on different streams take different tensors.  starts
+        is always exact; entries at and past the capacity are not written."""
+        offs = vp(offsets.data_ptr()) if offsets is not None else None
+        cap = int(index.numel()) if index is not None else 0
+        wb = int(work.numel() * work.element_size()) if work is not None else 0
+        _check(lib().lsmb_lset_probe_lists_dev(self.h, vp(data.data_ptr()), offs, key_len, n, vp(starts.data_ptr()),
+                                               vp(index.data_ptr()) if cap else None, cap,
+                                               vp(work.data_ptr()) if wb else None, wb, Context._stream(stream)))
 
 
 def build_strategy(num_bits, n, k=7):
