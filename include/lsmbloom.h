@@ -250,6 +250,15 @@ int lsmb_build_fixed_dev_sweep_new(lsmb_ctx* ctx, const void* d_keys, uint32_t k
 uint32_t lsmb_crc32(uint32_t crc, const uint8_t* data, uint64_t len);
 uint32_t lsmb_crc32_combine(uint32_t crc_a, uint32_t crc_b, uint64_t len_b);
 int lsmb_crc32_dev(lsmb_ctx* ctx, uint32_t crc, const void* d_data, uint64_t len, uint32_t* out, void* stream);
+/* Many device segments in one launch (the bloom blocks of the SSTables a store
+ * opens, SSTable::open -> deserialize, src/sstable/reader.rs:78-82, ~1 KB
+ * each): d_segs is nseg pairs {const void* data; uint64_t len} in device
+ * memory, d_out[s] = the CRC-32 (src/wal/record.rs:96) of segment s, uint32_t
+ * in device memory.  One wave per segment: meant for segments up to 128 KiB,
+ * exact for any length; 16-byte-aligned segments take the wide loads.
+ * Asynchronous on `stream`, no host synchronisation inside.  This is what
+ * lsmb_lset_add_batch checks its CRCs with. */
+int lsmb_crc32_seg_dev(lsmb_ctx* ctx, const void* d_segs, uint64_t nseg, void* d_out, void* stream);
 int lsmb_build_block_crc(lsmb_ctx* ctx, const uint8_t* data, const uint64_t* offsets, uint32_t key_len, uint64_t n,
                          uint32_t num_bits, uint32_t num_hashes, uint8_t* block, uint64_t block_len, uint32_t* crc);
 
@@ -498,7 +507,8 @@ int lsmb_fset_probe_lists(lsmb_fset* fs, const uint8_t* data, const uint64_t* of
  * mask bit per table: a row of thousands of tables costs each key one binary
  * search, one range check and at most one filter walk.  Filters may have any
  * (num_bits, num_hashes), num_hashes = 0 and > 8 included.
- *   open -> add / add_words (any order) -> seal -> probe ... -> close
+ *   open -> add / add_words / add_batch (any order) -> seal -> probe ... -> close
+ *   derive (from a sealed set, sharing its filters) -> add ... -> seal -> probe ... -> close
  * A set belongs to one context.  Adds and seal are used from one thread at a
  * time; a sealed set is only read, so probes on different streams need no
  * ordering among themselves.  Close a set once its probes have completed. */
@@ -527,6 +537,45 @@ int lsmb_lset_add_words(lsmb_lset* ls, uint32_t row, uint32_t table_id, const ui
  * fails is LSMB_EINVAL, lsmb_last_error() naming the two offending table ids;
  * the set stays unsealed.  A set with no table seals too. */
 int lsmb_lset_seal(lsmb_lset* ls);
+
+/* Version edit (src/compaction/scheduler.rs:163-177: retain(!input_ids.contains(id)) over every
+ * level, then push): a new, UNSEALED set on parent's context holding every table of the sealed
+ * parent whose id is not in drop_ids (in any row; an id held by several tables drops them all;
+ * an id no table has is ignored), each in its row, with its range, SHARING the parent's device
+ * filter words: nothing is uploaded.  *dropped (may be NULL) = tables left out.
+ * lsmb_lset_rows(child) >= lsmb_lset_rows(parent), even if the top rows end up empty.
+ * Then add / add_batch / seal as for any set.  LSMB_EINVAL: NULL parent or out, unsealed parent,
+ * ndrop > 0 with NULL drop_ids.
+ * The shared words live in reference-counted arena chunks: a chunk is released when the last
+ * set holding one of its tables is closed, so parent and child may be closed in either order
+ * (each once its own probes have completed), and the parent may be probed on other threads
+ * while a child is derived.  A set writes only into chunks it allocated itself. */
+int lsmb_lset_derive(const lsmb_lset* parent, const uint32_t* drop_ids, uint64_t ndrop,
+                     uint64_t* dropped, lsmb_lset** out);
+
+/* ntab tables in one call (a store opening its SSTables, SSTable::open -> deserialize,
+ * src/sstable/reader.rs:78-82): table t goes to rows[t] with id table_ids[t]; its serialized block is
+ * blocks[block_off[t] .. block_off[t+1]), its min_key keys[key_off[2t] .. key_off[2t+1]), its
+ * max_key keys[key_off[2t+1] .. key_off[2t+2]).  crcs == NULL: unchecked, as lsmb_lset_add.
+ * crcs != NULL: crcs[t] is the CRC-32 (lsmb_crc32) of table t's whole block, checked on the
+ * copy in device memory.  ALL OR NOTHING: if any table fails (argument, header validation as
+ * lsmb_lset_add, CRC), the set is exactly as before the call, and the return is the code of the
+ * first failing table.  status (may be NULL) receives every table's own code (LSMB_OK,
+ * LSMB_EINVAL, LSMB_ECORRUPT), and lsmb_last_error() names the first failing index and id.
+ * ntab == 0 is LSMB_OK.  The words are staged in pinned memory and cross in at most one copy
+ * per arena chunk touched, with one synchronisation for the batch; CRCs are only checked
+ * once every header has passed. */
+int lsmb_lset_add_batch(lsmb_lset* ls, uint64_t ntab, const uint32_t* rows, const uint32_t* table_ids,
+                        const uint8_t* blocks, const uint64_t* block_off, const uint32_t* crcs,
+                        const uint8_t* keys, const uint64_t* key_off, int32_t* status);
+
+/* A set's footprint after a chain of version edits (src/compaction/scheduler.rs:163-177):
+ * out[0] tables; [1] tables inherited by lsmb_lset_derive; [2] filter bytes this set uploaded;
+ * [3] host-to-device copy calls this set issued for filter words; [4] device bytes of all arena
+ * chunks this set keeps alive (its own and shared ones); [5] filter bytes of its tables.
+ * [5]/[4] is the occupancy.  A caller rebuilds a fresh set when a long chain of edits has left
+ * it low.  LSMB_EINVAL: NULL set or out. */
+int lsmb_lset_stats(const lsmb_lset* ls, uint64_t out[6]);
 
 /* 1 + the highest row added (0 when empty; 0 for NULL). */
 int lsmb_lset_rows(const lsmb_lset* ls);

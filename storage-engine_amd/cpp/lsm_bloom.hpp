@@ -281,6 +281,53 @@ class LevelSet {
     }
     // Sorts and checks the rows (std::invalid_argument naming two overlapping tables).
     void seal() { check(lsmb_lset_seal(ls_)); }
+
+    // Version edit (lsmb_lset_derive, src/compaction/scheduler.rs:163-177): a
+    // new, unsealed set holding every table of this sealed one whose id is not
+    // in drop_ids, sharing the device filter words.  Then add / add_many /
+    // seal; the two sets are destroyed in either order.
+    std::unique_ptr<LevelSet> derive(const std::vector<uint32_t>& drop_ids, uint64_t* dropped = nullptr) const {
+        lsmb_lset* h = nullptr;
+        check(lsmb_lset_derive(ls_, drop_ids.data(), drop_ids.size(), dropped, &h));
+        return std::unique_ptr<LevelSet>(new LevelSet(h));
+    }
+    // Many tables in one call (lsmb_lset_add_batch): all or nothing; crcs
+    // (optional) are checked on the device copies.  Throws as add does for the
+    // first failing table; status (optional) receives every table's own code.
+    struct TableRange {
+        std::string min_key, max_key;
+    };
+    void add_many(const std::vector<uint32_t>& rows, const std::vector<uint32_t>& table_ids,
+                  const std::vector<std::vector<uint8_t>>& blocks, const std::vector<TableRange>& ranges,
+                  const std::vector<uint32_t>* crcs = nullptr, std::vector<int32_t>* status = nullptr) {
+        const size_t n = blocks.size();
+        if (rows.size() != n || table_ids.size() != n || ranges.size() != n || (crcs && crcs->size() != n))
+            throw std::invalid_argument("add_many: rows, table_ids, blocks, ranges and crcs differ in length");
+        std::vector<uint8_t> bb, kb;
+        std::vector<uint64_t> boff(n + 1, 0), koff(2 * n + 1, 0);
+        for (size_t t = 0; t < n; t++) {
+            bb.insert(bb.end(), blocks[t].begin(), blocks[t].end());
+            boff[t + 1] = bb.size();
+            kb.insert(kb.end(), ranges[t].min_key.begin(), ranges[t].min_key.end());
+            koff[2 * t + 1] = kb.size();
+            kb.insert(kb.end(), ranges[t].max_key.begin(), ranges[t].max_key.end());
+            koff[2 * t + 2] = kb.size();
+        }
+        bb.push_back(0);
+        kb.push_back(0);
+        if (status) status->assign(n, 0);
+        check(lsmb_lset_add_batch(ls_, n, rows.data(), table_ids.data(), bb.data(), boff.data(),
+                                  crcs ? crcs->data() : nullptr, kb.data(), koff.data(),
+                                  status && n ? status->data() : nullptr));
+    }
+    // lsmb_lset_stats: [0] tables, [1] inherited by derive, [2] filter bytes
+    // and [3] copy calls of this set's own uploads, [4] device bytes of the
+    // arena chunks it keeps alive, [5] filter bytes of its tables.
+    std::array<uint64_t, 6> stats() const {
+        std::array<uint64_t, 6> s{};
+        check(lsmb_lset_stats(ls_, s.data()));
+        return s;
+    }
     int rows() const { return lsmb_lset_rows(ls_); }
     uint64_t tables(uint32_t row) const { return lsmb_lset_tables(ls_, row); }
 
@@ -349,6 +396,7 @@ class LevelSet {
     }
 
    private:
+    explicit LevelSet(lsmb_lset* h) : ls_(h) {}  // derive
     static const uint8_t* u8(std::string_view s) { return reinterpret_cast<const uint8_t*>(s.data()); }
     lsmb_lset* ls_ = nullptr;
 };

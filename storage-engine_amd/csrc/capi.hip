@@ -12,10 +12,12 @@
 
 #include <algorithm>
 #include <atomic>
+#include <memory>
 #include <string>
 #include <thread>
 #include <vector>
 
+#include "crc_seg.hpp"
 #include "ctx.hpp"
 #include "lset_lists_plan.hpp"
 #include "lset_order.hpp"
@@ -1148,19 +1150,50 @@ int lsmb_fset_probe_lists(lsmb_fset* fs, const uint8_t* data, const uint64_t* of
 // order, each filter copied into a device arena as it arrives; seal sorts the
 // rows, checks them (lset_order.hpp) and uploads the descriptors.  A sealed
 // set is only read, so its probes need no scratch and no ordering.
+//
+// A Version edit (src/compaction/scheduler.rs:163-177) derives the next set
+// from a sealed one: the child holds the surviving tables with their device
+// words where they are, so the arena chunks are reference-counted (the counts
+// are shared_ptr's, atomic: a parent may be probed while a child is derived)
+// and a chunk goes when the last set holding one of its tables is closed.  A
+// set bump-allocates only in chunks it allocated itself (own_tail), never in
+// the tail of an inherited one: two children of one parent would collide
+// there, and a sealed set's memory stays read-only for probes in flight.
+namespace lsmb {
+struct LsetChunk {
+    int dev = 0;
+    DevBuf buf;
+    ~LsetChunk() {  // the last set holding the chunk closes (or a failed batch gives its chunks back)
+        DevGuard g(dev);
+        buf.release();
+    }
+};
+}  // namespace lsmb
+
 struct lsmb_lset {
     lsmb_ctx* c = nullptr;
     struct Table {
         uint32_t id = 0, num_bits = 0, k = 0;
+        uint32_t chunk = 0;               // index into chunks
         const uint32_t* words = nullptr;  // in the arena
         std::vector<uint8_t> lo, hi;
     };
     std::vector<Table> row[kLsetMaxRows];
     uint32_t nrows = 0;  // 1 + highest row added
     bool sealed = false;
-    // filter words: bump-allocated from chunks that are never reallocated
-    std::vector<DevBuf> chunks;
+    // filter words: bump-allocated from chunks that are never reallocated;
+    // a derived set's inherited chunks come first
+    std::vector<std::shared_ptr<LsetChunk>> chunks;
     size_t chunk_used = 0;
+    bool own_tail = false;  // chunks.back() is this set's own: the bump pointer may advance in it
+    // lsmb_lset_stats: tables taken over by derive, filter bytes and copy calls of this set's uploads
+    uint64_t inherited = 0, up_bytes = 0, up_copies = 0;
+    // lsmb_lset_add_batch: pinned staging (words in the arena's layout, CRC
+    // segments and results) and the device side of the CRC check
+    uint8_t* pin = nullptr;
+    size_t pin_cap = 0;
+    PinnedPool pin_retired;
+    DevBuf segs;
     DevBuf bounds, desc, pfx;  // seal: the bound keys' bytes, LsetTable[], prefix pairs
     LsetRows rows{};
     // seal: the table id of every ordinal (row by row, each in its sealed
@@ -1176,15 +1209,21 @@ constexpr size_t kLsetChunkBytes = 4u << 20;
 
 // 16-B-aligned device memory for one filter's words (a filter larger than a
 // chunk gets a chunk of its own).
-int lset_arena_alloc(lsmb_lset* ls, size_t bytes, void** out) {
-    bytes = (std::max<size_t>(bytes, 8) + 15) & ~(size_t)15;
-    if (ls->chunks.empty() || ls->chunk_used + bytes > ls->chunks.back().bytes) {
-        DevBuf b;
-        HIP_TRY(b.ensure(std::max(bytes, kLsetChunkBytes)));
-        ls->chunks.push_back(b);
+inline size_t lset_slot_bytes(uint64_t nw) { return (std::max<size_t>(nw * 8, 8) + 15) & ~(size_t)15; }
+
+int lset_arena_alloc(lsmb_lset* ls, size_t bytes, void** out, uint32_t* chunk) {
+    bytes = lset_slot_bytes(bytes / 8);
+    if (!ls->own_tail || ls->chunk_used + bytes > ls->chunks.back()->buf.bytes) {
+        if (ls->chunks.size() >= UINT32_MAX) return fail(LSMB_EINVAL, "level set arena is full");
+        auto ch = std::make_shared<LsetChunk>();
+        ch->dev = ls->c->dev;
+        HIP_TRY(ch->buf.ensure(std::max(bytes, kLsetChunkBytes)));
+        ls->chunks.push_back(std::move(ch));
         ls->chunk_used = 0;
+        ls->own_tail = true;
     }
-    *out = (uint8_t*)ls->chunks.back().p + ls->chunk_used;
+    *out = (uint8_t*)ls->chunks.back()->buf.p + ls->chunk_used;
+    *chunk = (uint32_t)(ls->chunks.size() - 1);
     ls->chunk_used += bytes;
     return LSMB_OK;
 }
@@ -1198,15 +1237,19 @@ int lset_add_common(lsmb_lset* ls, uint32_t row, uint32_t table_id, const uint8_
     DevGuard g(ls->c->dev);
     const uint64_t nw = nwords64(num_bits);
     void* dw = nullptr;
-    if (int rc = lset_arena_alloc(ls, nw * 8, &dw)) return rc;
+    uint32_t chunk = 0;
+    if (int rc = lset_arena_alloc(ls, nw * 8, &dw, &chunk)) return rc;
     if (nw) {
         HIP_TRY(hipMemcpyAsync(dw, words_le, nw * 8, hipMemcpyHostToDevice, ls->ust));
         HIP_TRY(hipStreamSynchronize(ls->ust));  // the caller's block is free to go
+        ls->up_bytes += nw * 8;
+        ls->up_copies++;
     }
     lsmb_lset::Table t;
     t.id = table_id;
     t.num_bits = num_bits;
     t.k = k;
+    t.chunk = chunk;
     t.words = (const uint32_t*)dw;
     t.lo.assign(min_key, min_key + min_len);
     t.hi.assign(max_key, max_key + max_len);
@@ -1250,7 +1293,10 @@ void lsmb_lset_close(lsmb_lset* ls) {
     {
         DevGuard g(ls->c->dev);
         if (ls->ust) hipStreamSynchronize(ls->ust), hipStreamDestroy(ls->ust);
-        for (auto& b : ls->chunks) b.release();
+        ls->chunks.clear();  // each chunk goes with the last set holding it
+        ls->segs.release();
+        if (ls->pin) (void)hipHostFree(ls->pin);  // teardown
+        ls->pin_retired.release();
         ls->bounds.release();
         ls->desc.release();
         ls->pfx.release();
@@ -1273,6 +1319,238 @@ int lsmb_lset_add_words(lsmb_lset* ls, uint32_t row, uint32_t table_id, const ui
     if (!words && nwords64(num_bits)) return fail(LSMB_EINVAL, "null words");
     return lset_add_common(ls, row, table_id, (const uint8_t*)words, num_bits, num_hashes, min_key, min_len, max_key,
                            max_len);
+}
+
+int lsmb_lset_derive(const lsmb_lset* parent, const uint32_t* drop_ids, uint64_t ndrop, uint64_t* dropped,
+                     lsmb_lset** out) {
+    if (out) *out = nullptr;
+    if (!parent || !out) return fail(LSMB_EINVAL, "null argument");
+    if (!parent->sealed) return fail(LSMB_EINVAL, "derive from an unsealed level set");
+    if (ndrop && !drop_ids) return fail(LSMB_EINVAL, "null drop_ids");
+    std::vector<uint32_t> drop(drop_ids, drop_ids + ndrop);
+    std::sort(drop.begin(), drop.end());
+    lsmb_lset* ls = nullptr;
+    if (int rc = lsmb_lset_open(parent->c, &ls)) return rc;
+    // the surviving tables, each in its row, and only the chunks that hold one
+    std::vector<uint32_t> remap(parent->chunks.size(), UINT32_MAX);
+    uint64_t nd = 0;
+    for (uint32_t r = 0; r < parent->nrows; r++)
+        for (const auto& T : parent->row[r]) {
+            if (std::binary_search(drop.begin(), drop.end(), T.id)) {
+                nd++;
+                continue;
+            }
+            if (remap[T.chunk] == UINT32_MAX) {
+                remap[T.chunk] = (uint32_t)ls->chunks.size();
+                ls->chunks.push_back(parent->chunks[T.chunk]);
+            }
+            ls->row[r].push_back(T);
+            ls->row[r].back().chunk = remap[T.chunk];
+            ls->inherited++;
+        }
+    ls->nrows = parent->nrows;
+    if (dropped) *dropped = nd;
+    *out = ls;
+    return LSMB_OK;
+}
+
+namespace {
+
+// One table of a batch after its host-side checks.
+struct LsetBatchItem {
+    uint32_t nb = 0, k = 0;
+    uint64_t nw = 0;
+    uint8_t* dw = nullptr;   // its slot in the arena
+    uint32_t chunk = 0;
+    size_t stage = 0;        // its words in the pinned staging
+};
+
+// A run of slots in one chunk: one host-to-device copy.
+struct LsetBatchSpan {
+    uint32_t chunk;
+    uint8_t* lo;
+    size_t bytes, stage;
+};
+
+int lset_batch_check_one(const lsmb_lset* ls, uint64_t ntab, uint32_t row, uint32_t id, const uint8_t* blocks,
+                         const uint64_t* boff, const uint8_t* keys, const uint64_t* koff, LsetBatchItem* it) {
+    if (int rc = lset_add_check(ls, row, id)) return rc;
+    if (boff[1] < boff[0]) return fail(LSMB_EINVAL, "block offsets descend");
+    uint32_t nw32 = 0;
+    if (int rc = lsmb_deserialize_header(blocks ? blocks + boff[0] : nullptr, boff[1] - boff[0], &it->k, &it->nb, &nw32))
+        return rc;
+    it->nw = nw32;
+    if (int rc = check_filter(it->nb, it->k)) return rc;
+    if (koff[1] < koff[0] || koff[2] < koff[1]) return fail(LSMB_EINVAL, "key offsets descend");
+    if (koff[2] > koff[0] && !keys) return fail(LSMB_EINVAL, "null key range");
+    if (koff[1] - koff[0] > UINT32_MAX || koff[2] - koff[1] > UINT32_MAX) return fail(LSMB_EINVAL, "range key too long");
+    if (ls->row[row].size() + ntab >= UINT32_MAX) return fail(LSMB_EINVAL, "level set row %u is full", row);
+    return LSMB_OK;
+}
+
+int lset_pin_ensure(lsmb_lset* ls, size_t need) {
+    if (need <= ls->pin_cap) return LSMB_OK;
+    const size_t cap = std::max(need, ls->pin_cap + ls->pin_cap / 2);
+    void* q = nullptr;
+    if (hipHostMalloc(&q, cap, hipHostMallocDefault) != hipSuccess) {
+        (void)hipGetLastError();
+        return fail(LSMB_ENOMEM, "level set: %llu bytes of pinned staging", (unsigned long long)cap);
+    }
+    ls->pin_retired.retire(ls->pin);  // freed at close
+    ls->pin = (uint8_t*)q;
+    ls->pin_cap = cap;
+    return LSMB_OK;
+}
+
+// Slots, staging, copies and the CRC check of a batch whose headers passed.
+// On any error the caller rolls the arena back.
+int lset_batch_upload(lsmb_lset* ls, uint64_t ntab, const uint32_t* ids, const uint8_t* blocks, const uint64_t* boff,
+                      const uint32_t* crcs, int32_t* status, std::vector<LsetBatchItem>& items, uint64_t* up_bytes,
+                      uint64_t* up_copies) {
+    // slots in the arena, 16-B aligned, and the runs they form per chunk
+    std::vector<LsetBatchSpan> spans;
+    size_t stage = 0;
+    for (uint64_t t = 0; t < ntab; t++) {
+        LsetBatchItem& it = items[t];
+        void* dw = nullptr;
+        if (int rc = lset_arena_alloc(ls, it.nw * 8, &dw, &it.chunk)) return rc;
+        it.dw = (uint8_t*)dw;
+        const size_t slot = lset_slot_bytes(it.nw);
+        if (spans.empty() || spans.back().chunk != it.chunk) spans.push_back(LsetBatchSpan{it.chunk, it.dw, 0, stage});
+        it.stage = stage;
+        spans.back().bytes += slot;
+        stage += slot;
+    }
+    // the CRC segments (up to 128 KiB each: one wave per segment) and their results after the words
+    std::vector<uint64_t> seg_of;
+    if (crcs)
+        for (uint64_t t = 0; t < ntab; t++)
+            if (items[t].nw * 8 <= kCrcSegWaveMax) seg_of.push_back(t);
+    const size_t nseg = seg_of.size();
+    const size_t seg_at = stage, out_at = seg_at + nseg * sizeof(CrcSeg);
+    if (int rc = lset_pin_ensure(ls, out_at + nseg * 4 + 16)) return rc;
+    for (uint64_t t = 0; t < ntab; t++) {
+        const LsetBatchItem& it = items[t];
+        const size_t slot = lset_slot_bytes(it.nw);
+        if (it.nw) memcpy(ls->pin + it.stage, blocks + boff[t] + 12, it.nw * 8);
+        memset(ls->pin + it.stage + it.nw * 8, 0, slot - it.nw * 8);
+    }
+    for (const auto& sp : spans) {  // one copy per chunk touched
+        HIP_TRY(hipMemcpyAsync(sp.lo, ls->pin + sp.stage, sp.bytes, hipMemcpyHostToDevice, ls->ust));
+        (*up_copies)++;
+    }
+    for (uint64_t t = 0; t < ntab; t++) *up_bytes += items[t].nw * 8;
+    if (nseg) {
+        CrcSeg* hs = (CrcSeg*)(ls->pin + seg_at);
+        for (size_t s = 0; s < nseg; s++) hs[s] = CrcSeg{items[seg_of[s]].dw, items[seg_of[s]].nw * 8};
+        HIP_TRY(ls->segs.ensure(nseg * (sizeof(CrcSeg) + 4)));
+        uint8_t* ds = (uint8_t*)ls->segs.p;
+        uint32_t* dout = (uint32_t*)(ds + nseg * sizeof(CrcSeg));
+        HIP_TRY(hipMemcpyAsync(ds, hs, nseg * sizeof(CrcSeg), hipMemcpyHostToDevice, ls->ust));
+        if (int rc = crc32_seg_dev((const CrcSeg*)ds, nseg, dout, ls->ust)) return rc;
+        HIP_TRY(hipMemcpyAsync(ls->pin + out_at, dout, nseg * 4, hipMemcpyDeviceToHost, ls->ust));
+    }
+    HIP_TRY(hipStreamSynchronize(ls->ust));  // the batch's one wait: the caller's blocks are free to go
+    if (!crcs) return LSMB_OK;
+    // the copies now in HBM, not the host bytes, are what probes will read
+    std::vector<uint32_t> words_crc(ntab, 0);
+    const uint32_t* hout = (const uint32_t*)(ls->pin + out_at);
+    for (size_t s = 0; s < nseg; s++) words_crc[seg_of[s]] = hout[s];
+    for (uint64_t t = 0; t < ntab; t++)
+        if (items[t].nw * 8 > kCrcSegWaveMax)
+            if (int rc = crc32_dev(ls->c, items[t].dw, items[t].nw * 8, 0, ls->ust, &words_crc[t])) return rc;
+    int first = LSMB_OK;
+    uint64_t f_len = 0;
+    uint32_t f = 1u << 31;  // x^(8·f_len): the tables of a store mostly share one size
+    for (uint64_t t = 0; t < ntab; t++) {
+        if (items[t].nw * 8 != f_len) f = x8nmodp(f_len = items[t].nw * 8);
+        const uint32_t got = multmodp(f, crc32_host(blocks + boff[t], 12, 0)) ^ words_crc[t];  // header ‖ words
+        if (got == crcs[t]) continue;
+        if (status) status[t] = LSMB_ECORRUPT;
+        if (first == LSMB_OK)
+            first = fail(LSMB_ECORRUPT,
+                         "table %llu of the batch (id %u): bloom block CRC-32 mismatch: expected %08x, device copy %08x",
+                         (unsigned long long)t, ids[t], crcs[t], got);
+    }
+    return first;
+}
+
+}  // namespace
+
+int lsmb_lset_add_batch(lsmb_lset* ls, uint64_t ntab, const uint32_t* rows, const uint32_t* table_ids,
+                        const uint8_t* blocks, const uint64_t* block_off, const uint32_t* crcs, const uint8_t* keys,
+                        const uint64_t* key_off, int32_t* status) {
+    if (!ls) return fail(LSMB_EINVAL, "null level set");
+    if (ls->sealed) return fail(LSMB_EINVAL, "level set is sealed: a new Version takes a new set");
+    if (ntab == 0) return LSMB_OK;
+    if (!rows || !table_ids || !block_off || !key_off) return fail(LSMB_EINVAL, "null argument");
+    if (ntab >= UINT32_MAX) return fail(LSMB_EINVAL, "more than 2^32-2 tables in one batch");
+    // every header on the host first: nothing is allocated or uploaded for a batch that fails here
+    std::vector<LsetBatchItem> items(ntab);
+    int first_rc = LSMB_OK;
+    uint64_t first_t = 0;
+    std::string first_msg;
+    for (uint64_t t = 0; t < ntab; t++) {
+        const int rc = lset_batch_check_one(ls, ntab, rows[t], table_ids[t], blocks, block_off + t, keys,
+                                            key_off + 2 * t, &items[t]);
+        if (status) status[t] = rc;
+        if (rc && first_rc == LSMB_OK) {
+            first_rc = rc;
+            first_t = t;
+            first_msg = last_error();
+        }
+    }
+    if (first_rc)
+        return fail(first_rc, "table %llu of the batch (id %u): %s", (unsigned long long)first_t, table_ids[first_t],
+                    first_msg.c_str());
+    DevGuard g(ls->c->dev);
+    const size_t chunks0 = ls->chunks.size(), used0 = ls->chunk_used;
+    const bool own0 = ls->own_tail;
+    uint64_t up_bytes = 0, up_copies = 0;
+    if (int rc = lset_batch_upload(ls, ntab, table_ids, blocks, block_off, crcs, status, items, &up_bytes, &up_copies)) {
+        // all or nothing: the bump pointer back, this call's chunks gone, no table appended
+        const std::string msg = last_error();
+        (void)hipStreamSynchronize(ls->ust);
+        ls->chunks.resize(chunks0);
+        ls->chunk_used = used0;
+        ls->own_tail = own0;
+        set_last_error(msg);
+        return rc;
+    }
+    for (uint64_t t = 0; t < ntab; t++) {
+        const LsetBatchItem& it = items[t];
+        lsmb_lset::Table T;
+        T.id = table_ids[t];
+        T.num_bits = it.nb;
+        T.k = it.k;
+        T.chunk = it.chunk;
+        T.words = (const uint32_t*)it.dw;
+        const uint64_t* ko = key_off + 2 * t;
+        if (ko[1] > ko[0]) T.lo.assign(keys + ko[0], keys + ko[1]);
+        if (ko[2] > ko[1]) T.hi.assign(keys + ko[1], keys + ko[2]);
+        ls->row[rows[t]].push_back(std::move(T));
+        ls->nrows = std::max(ls->nrows, rows[t] + 1);
+    }
+    ls->up_bytes += up_bytes;
+    ls->up_copies += up_copies;
+    return LSMB_OK;
+}
+
+int lsmb_lset_stats(const lsmb_lset* ls, uint64_t out[6]) {
+    if (!ls || !out) return fail(LSMB_EINVAL, "null argument");
+    uint64_t ntab = 0, fbytes = 0, cbytes = 0;
+    for (uint32_t r = 0; r < ls->nrows; r++) {
+        ntab += ls->row[r].size();
+        for (const auto& T : ls->row[r]) fbytes += nwords64(T.num_bits) * 8;
+    }
+    for (const auto& ch : ls->chunks) cbytes += ch->buf.bytes;
+    out[0] = ntab;
+    out[1] = ls->inherited;
+    out[2] = ls->up_bytes;
+    out[3] = ls->up_copies;
+    out[4] = cbytes;
+    out[5] = fbytes;
+    return LSMB_OK;
 }
 
 int lsmb_lset_seal(lsmb_lset* ls) {

@@ -9,73 +9,25 @@
 // workgroup combines its 256 pieces in a tree (CRC(A‖B) = CRC(A)·x^(8|B|) ⊕
 // CRC(B) in GF(2)[x] mod P, the combine of zlib's crc32_combine); the host
 // combines the workgroups' CRCs in order.  A 120 MB C2 block is 915 workgroups.
+//
+// Many small blocks (a level set's SSTable filters, ~1 KB each): k_crc32_seg,
+// one wave per segment and four segments per workgroup, the wave's 64 pieces
+// combined in a shuffle tree, every segment's CRC from one launch.  The
+// products, the piece geometry and a serial statement of the tree are in
+// crc_seg.hpp, where a CPU test drives them.
 #include <string.h>
 
 #include <vector>
 
+#include "crc_seg.hpp"
 #include "ctx.hpp"
 
 namespace lsmb {
 namespace {
 
-constexpr uint32_t kPoly = 0xEDB88320u;
 constexpr uint32_t kCrcLanes = 256, kCrcPiece = 512;         // bytes per lane
 constexpr uint64_t kCrcBlock = (uint64_t)kCrcLanes * kCrcPiece;  // bytes per workgroup
-
-// a·b mod P, reflected bit order (bit 31 = x^0).
-LSMB_HD uint32_t multmodp(uint32_t a, uint32_t b) {
-    uint32_t p = 0;
-    for (uint32_t m = 1u << 31; m && a; m >>= 1) {
-        if (a & m) {
-            p ^= b;
-            a ^= m;
-        }
-        b = (b & 1) ? (b >> 1) ^ kPoly : b >> 1;
-    }
-    return p;
-}
-
-// x^(8 n) mod P: square-and-multiply over x^(2^k) (x^1 = 0x40000000).
-LSMB_HD uint32_t x8nmodp(uint64_t n) {
-    uint32_t x2k = 0x40000000u;  // x^(2^0)
-    // x^8 = x^(2^3): square three times
-    for (int i = 0; i < 3; i++) x2k = multmodp(x2k, x2k);
-    uint32_t p = 1u << 31;  // x^0
-    while (n) {
-        if (n & 1) p = multmodp(x2k, p);
-        n >>= 1;
-        x2k = multmodp(x2k, x2k);
-    }
-    return p;
-}
-
-// CRC(A‖B) from CRC(A), CRC(B) and |B| (standard, pre/post-inverted CRCs).
-LSMB_HD uint32_t crc_combine(uint32_t crc_a, uint32_t crc_b, uint64_t len_b) {
-    return multmodp(x8nmodp(len_b), crc_a) ^ crc_b;
-}
-
-struct CrcTables {
-    uint32_t t[4][256];
-};
-
-void make_tables(CrcTables& T) {
-    for (uint32_t i = 0; i < 256; i++) {
-        uint32_t c = i;
-        for (int j = 0; j < 8; j++) c = (c & 1) ? (c >> 1) ^ kPoly : c >> 1;
-        T.t[0][i] = c;
-    }
-    for (uint32_t i = 0; i < 256; i++)
-        for (int s = 1; s < 4; s++) T.t[s][i] = (T.t[s - 1][i] >> 8) ^ T.t[0][T.t[s - 1][i] & 0xFF];
-}
-
-const CrcTables& tables() {
-    static const CrcTables T = [] {
-        CrcTables t;
-        make_tables(t);
-        return t;
-    }();
-    return T;
-}
+static_assert(kCrcBlock == kCrcSegWaveMax, "segments past k_crc32_seg's range are whole k_crc32 blocks");
 
 // The x^(8·512·2^l) factors of the workgroup tree (l = 0..7), for full pieces.
 struct TreePowers {
@@ -96,7 +48,7 @@ __global__ __launch_bounds__(kCrcLanes) void k_crc32(const uint8_t* __restrict__
     const uint32_t lane = threadIdx.x;
     {  // slicing-by-4 tables, one entry per lane
         uint32_t c0 = lane;
-        for (int j = 0; j < 8; j++) c0 = (c0 & 1) ? (c0 >> 1) ^ kPoly : c0 >> 1;
+        for (int j = 0; j < 8; j++) c0 = (c0 & 1) ? (c0 >> 1) ^ kCrcPoly : c0 >> 1;
         t[0][lane] = c0;
         __syncthreads();
         for (int s = 1; s < 4; s++) {
@@ -153,10 +105,62 @@ __global__ __launch_bounds__(kCrcLanes) void k_crc32(const uint8_t* __restrict__
     if (lane == 0) out[blockIdx.x] = part[0];
 }
 
+// Wave w of workgroup b: out[s] = CRC-32 of segment s = 4 b + w (crc_seg.hpp:
+// the whole pieces right-justified on the lanes, six shuffle levels with one
+// factor each, the tail appended last; crc_seg_ref is this, serially).
+__global__ __launch_bounds__(kCrcSegLanes* kCrcSegPerBlock) void k_crc32_seg(const CrcSeg* __restrict__ segs,
+                                                                              uint64_t nseg,
+                                                                              uint32_t* __restrict__ out) {
+    __shared__ uint32_t t[4][256];
+    static_assert(kCrcSegLanes * kCrcSegPerBlock == 256, "one table entry per lane");
+    {  // slicing-by-4 tables, one entry per lane
+        const uint32_t i = threadIdx.x;
+        uint32_t c0 = i;
+        for (int j = 0; j < 8; j++) c0 = (c0 & 1) ? (c0 >> 1) ^ kCrcPoly : c0 >> 1;
+        t[0][i] = c0;
+        __syncthreads();
+        for (int s = 1; s < 4; s++) {
+            t[s][i] = (t[s - 1][i] >> 8) ^ t[0][t[s - 1][i] & 0xFF];
+            __syncthreads();
+        }
+    }
+    const uint32_t lane = threadIdx.x % kCrcSegLanes;
+    const uint64_t s = (uint64_t)blockIdx.x * kCrcSegPerBlock + threadIdx.x / kCrcSegLanes;
+    if (s >= nseg) return;  // whole waves, after the last barrier
+    const CrcSeg sg = segs[s];
+    const CrcSegGeom g = crc_seg_geom(sg.len);
+    uint64_t off;
+    const uint64_t n = crc_seg_lane(g, lane, &off);
+    const bool al = (reinterpret_cast<uintptr_t>(sg.p) & 15) == 0;
+    uint32_t c = crc_piece(t, sg.p + off, n, al);
+    // the tail's CRC to every lane and out of the tree (lane 0 when there is none: unused)
+    const uint32_t tail_crc = __shfl(c, g.tail ? (int)(kCrcSegLanes - g.nfull - 1) : 0);
+    if (crc_seg_is_tail_lane(g, lane)) c = 0;
+    uint32_t pw = x8nmodp(g.P);
+    for (uint32_t l = 0; l < kCrcSegLevels; l++) {
+        const uint32_t step = 1u << l;
+        const uint32_t right = __shfl_down(c, step);  // all 64 lanes take part
+        if ((lane & (2 * step - 1)) == 0) c = crc_seg_merge(c, right, pw);
+        if (l + 1 < kCrcSegLevels) pw = multmodp(pw, pw);
+    }
+    if (lane == 0) out[s] = crc_seg_finish(g, c, tail_crc);
+}
+
 }  // namespace
 
+// out[s] = CRC-32 of the device bytes segs[s] (segs and out in device memory),
+// one launch on st; nothing is synchronised.
+int crc32_seg_dev(const CrcSeg* d_segs, uint64_t nseg, uint32_t* d_out, hipStream_t st) {
+    if (nseg == 0) return LSMB_OK;
+    const uint64_t nwg = (nseg + kCrcSegPerBlock - 1) / kCrcSegPerBlock;
+    if (nwg > 0x7FFFFFFFull) return fail(LSMB_EINVAL, "crc32: %llu segments are too many", (unsigned long long)nseg);
+    k_crc32_seg<<<dim3((uint32_t)nwg), dim3(kCrcSegLanes * kCrcSegPerBlock), 0, st>>>(d_segs, nseg, d_out);
+    HIP_TRY(hipGetLastError());
+    return LSMB_OK;
+}
+
 uint32_t crc32_host(const uint8_t* p, uint64_t len, uint32_t crc) {
-    const CrcTables& T = tables();
+    const CrcTables& T = crc_tables();
     uint32_t c = ~crc;
     uint64_t i = 0;
     for (; i + 4 <= len; i += 4) {
@@ -215,6 +219,14 @@ int lsmb_crc32_dev(lsmb_ctx* c, uint32_t crc, const void* d_data, uint64_t len, 
     if (len && !d_data) return fail(LSMB_EINVAL, "null device pointer");
     DevGuard g(c->dev);
     return crc32_dev(c, (const uint8_t*)d_data, len, crc, stream ? (hipStream_t)stream : c->st, out);
+}
+
+int lsmb_crc32_seg_dev(lsmb_ctx* c, const void* d_segs, uint64_t nseg, void* d_out, void* stream) {
+    static_assert(sizeof(CrcSeg) == 16, "the ABI's (pointer, length) pairs");
+    if (!c) return fail(LSMB_EINVAL, "null argument");
+    if (nseg && (!d_segs || !d_out)) return fail(LSMB_EINVAL, "null device pointer");
+    DevGuard g(c->dev);
+    return crc32_seg_dev((const CrcSeg*)d_segs, nseg, (uint32_t*)d_out, stream ? (hipStream_t)stream : c->st);
 }
 
 }  // extern "C"

@@ -163,6 +163,10 @@ void report_stats(lsmb_ctx* c);
 // CRC-32 (crc32fast::hash / zlib crc32) of device bytes appended to `crc`
 // (crc32.hip); synchronises `st`.
 int crc32_dev(lsmb_ctx* c, const uint8_t* d, uint64_t len, uint32_t crc, hipStream_t st, uint32_t* out);
+// CRC-32 of every device segment (pointer, length) of d_segs into d_out, both
+// in device memory: one launch of k_crc32_seg on st, nothing synchronised.
+struct CrcSeg;
+int crc32_seg_dev(const CrcSeg* d_segs, uint64_t nseg, uint32_t* d_out, hipStream_t st);
 uint32_t crc32_host(const uint8_t* p, uint64_t len, uint32_t crc);
 uint32_t crc32_combine_host(uint32_t crc_a, uint32_t crc_b, uint64_t len_b);
 

@@ -64,6 +64,7 @@ SIGNATURES = {
     "lsmb_crc32": (ctypes.c_uint32, [ctypes.c_uint32, u8p, ctypes.c_uint64]),
     "lsmb_crc32_combine": (ctypes.c_uint32, [ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint64]),
     "lsmb_crc32_dev": (ctypes.c_int, [vp, ctypes.c_uint32, vp, ctypes.c_uint64, u32p, vp]),
+    "lsmb_crc32_seg_dev": (ctypes.c_int, [vp, vp, ctypes.c_uint64, vp, vp]),
     "lsmb_fset_add_crc": (ctypes.c_int, [vp, u8p, ctypes.c_uint64, ctypes.c_uint32, u8p, ctypes.c_uint64, u8p,
                                          ctypes.c_uint64]),
     "lsmb_probe": (ctypes.c_int, [vp, ctypes.POINTER(u64p), u32p, u32p, ctypes.c_uint32, u8p, u64p,
@@ -103,6 +104,10 @@ SIGNATURES = {
     "lsmb_lset_add_words": (ctypes.c_int, [vp, ctypes.c_uint32, ctypes.c_uint32, u64p, ctypes.c_uint32, ctypes.c_uint32,
                                            u8p, ctypes.c_uint64, u8p, ctypes.c_uint64]),
     "lsmb_lset_seal": (ctypes.c_int, [vp]),
+    "lsmb_lset_derive": (ctypes.c_int, [vp, u32p, ctypes.c_uint64, u64p, ctypes.POINTER(vp)]),
+    "lsmb_lset_add_batch": (ctypes.c_int, [vp, ctypes.c_uint64, u32p, u32p, u8p, u64p, u32p, u8p, u64p,
+                                           ctypes.POINTER(ctypes.c_int32)]),
+    "lsmb_lset_stats": (ctypes.c_int, [vp, u64p]),
     "lsmb_lset_rows": (ctypes.c_int, [vp]),
     "lsmb_lset_tables": (ctypes.c_uint64, [vp, ctypes.c_uint32]),
     "lsmb_lset_probe": (ctypes.c_int, [vp, u8p, u64p, ctypes.c_uint32, ctypes.c_uint64, u32p]),
@@ -336,6 +341,13 @@ class Context:
         out = ctypes.c_uint32()
         _check(lib().lsmb_crc32_dev(self.h, crc, vp(t.data_ptr()), n, ctypes.byref(out), self._stream(stream)))
         return out.value
+
+    def crc32_seg_dev(self, segs, nseg, out, stream=None):
+        """CRC-32 of nseg device segments in one launch (lsmb_crc32_seg_dev):
+        segs an int64 / uint64 device tensor of (pointer, byte length) pairs,
+        out an int32 / uint32 device tensor of nseg; asynchronous on stream."""
+        _check(lib().lsmb_crc32_seg_dev(self.h, vp(segs.data_ptr()), int(nseg), vp(out.data_ptr()),
+                                        self._stream(stream)))
 
     def probe(self, filters, data, offsets=None, key_len=0):
         """filters: [(words uint64 array, num_bits, k)] -> uint8 [n, ceil(F/8)] mask."""
@@ -727,6 +739,67 @@ class LevelSet:
 
     def seal(self):
         _check(lib().lsmb_lset_seal(self.h))
+
+    def derive(self, drop_ids=()):
+        """Version edit (lsmb_lset_derive): a new, unsealed LevelSet holding
+        every table of this sealed set whose id is not in drop_ids, sharing
+        the device filter words (nothing is uploaded).  Then add / add_many /
+        seal; this set and the new one are closed in either order.  The
+        number of tables left out is the new set's `dropped`."""
+        ids = np.ascontiguousarray(list(drop_ids), dtype=np.uint32)
+        h = vp()
+        nd = ctypes.c_uint64()
+        _check(lib().lsmb_lset_derive(self.h, _p(ids, u32p) if ids.size else None, ids.size,
+                                      ctypes.cast(ctypes.byref(nd), u64p), ctypes.byref(h)))
+        child = LevelSet.__new__(LevelSet)
+        child.ctx = self.ctx
+        child.h = h
+        child.dropped = int(nd.value)
+        return child
+
+    def add_many(self, rows, ids, blocks, ranges, crcs=None):
+        """Many tables in one call (lsmb_lset_add_batch): rows and ids per
+        table, blocks a list of serialized filters, ranges a list of
+        (min_key, max_key), crcs (optional) each block's CRC-32, checked on
+        the device copy.  All or nothing: raises as add does (Corruption,
+        ValueError) for the first failing table, the exception's `status`
+        holding every table's own code, and the set is unchanged; else
+        returns the status array (all LSMB_OK)."""
+        n = len(blocks)
+        if not (len(rows) == len(ids) == len(ranges) == n) or (crcs is not None and len(crcs) != n):
+            raise ValueError("add_many: rows, ids, blocks, ranges and crcs differ in length")
+        rows = np.ascontiguousarray(rows, dtype=np.uint32)
+        ids = np.ascontiguousarray(ids, dtype=np.uint32)
+        boff = np.zeros(n + 1, dtype=np.uint64)
+        np.cumsum([len(b) for b in blocks], out=boff[1:])
+        bb = np.frombuffer(b"".join(bytes(b) for b in blocks) + b"\0", dtype=np.uint8)
+        flat = [bytes(k) for lo_hi in ranges for k in lo_hi]
+        koff = np.zeros(2 * n + 1, dtype=np.uint64)
+        np.cumsum([len(k) for k in flat], out=koff[1:])
+        kb = np.frombuffer(b"".join(flat) + b"\0", dtype=np.uint8)
+        cc = None if crcs is None else np.ascontiguousarray(crcs, dtype=np.uint32)
+        status = np.zeros(max(n, 1), dtype=np.int32)
+        rc = lib().lsmb_lset_add_batch(self.h, n, _p(rows, u32p) if n else None, _p(ids, u32p) if n else None,
+                                       _p(bb, u8p), _p(boff, u64p), None if cc is None or not n else _p(cc, u32p),
+                                       _p(kb, u8p), _p(koff, u64p), _p(status, ctypes.POINTER(ctypes.c_int32)))
+        try:
+            _check(rc)
+        except (LsmbError, ValueError) as e:
+            e.status = status[:n]
+            raise
+        return status[:n]
+
+    def stats(self):
+        """lsmb_lset_stats: tables, inherited (by derive), uploaded_bytes and
+        upload_copies (this set's own filter uploads), chunk_bytes (device
+        bytes of the arena chunks it keeps alive, shared ones included),
+        filter_bytes (of its tables); occupancy = filter_bytes / chunk_bytes."""
+        out = np.zeros(6, dtype=np.uint64)
+        _check(lib().lsmb_lset_stats(self.h, _p(out, u64p)))
+        d = dict(zip(("tables", "inherited", "uploaded_bytes", "upload_copies", "chunk_bytes", "filter_bytes"),
+                     (int(x) for x in out)))
+        d["occupancy"] = d["filter_bytes"] / d["chunk_bytes"] if d["chunk_bytes"] else 0.0
+        return d
 
     def rows(self):
         return int(lib().lsmb_lset_rows(self.h))
