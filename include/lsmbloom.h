@@ -236,6 +236,66 @@ int lsmb_build_fixed_dev_sweep(lsmb_ctx* ctx, const void* d_keys, uint32_t key_l
 int lsmb_build_fixed_dev_sweep_new(lsmb_ctx* ctx, const void* d_keys, uint32_t key_len, uint64_t n,
                                    uint32_t num_bits, uint32_t num_hashes, void* d_words, int sweep, void* stream);
 
+/* ---- batched build: many SSTable filters from one key run ---------------- */
+/* The store sizes every SSTable's filter new(1000, 0.01) (src/sstable/builder.rs:74), fills it
+ * key by key (builder.rs:93) and serializes it at finish (builder.rs:177-182); a bulk load, a
+ * level rewritten with another false-positive rate or several compactions finishing together
+ * (src/compaction/scheduler.rs:147-177) produce many such tables at once.  These entry points
+ * build ntab independent filters from one run of n keys: table t is BloomFilter::new +
+ * insert of the keys [seg[t], seg[t+1]) of the run, in a filter of (num_bits[t],
+ * num_hashes[t]).  seg is non-decreasing with seg[ntab] <= n; keys outside every segment are
+ * ignored.  One kernel launch per geometry class, at most two, whatever ntab is.
+ *
+ * Packed layout: table t's u64 words start at word_off[t]; its slot is
+ * max(ceil(num_bits[t] / 64), 1) words rounded up to an even count (16-byte-aligned slots, the
+ * level set's arena rule), word_off[ntab] = the words of the whole buffer.  Every word of
+ * every slot is written (zero words and the pad word included): the buffer is output-only. */
+
+/* The largest num_bits a table of a batch may have (src/sstable/builder.rs:74 is far below it):
+ * 1 310 720, the filters the "lds" strategy serves.  A larger table takes
+ * lsmb_build_fixed_dev_new / lsmb_build_var_dev_new. */
+uint32_t lsmb_build_batch_max_bits(void);
+
+/* word_off[0 .. ntab] of the packed layout for these num_bits (the slots
+ * src/sstable/builder.rs:177-182's filters take in device memory).  LSMB_EINVAL: NULL word_off,
+ * NULL num_bits with ntab > 0. */
+int lsmb_build_batch_layout(uint64_t ntab, const uint32_t* num_bits, uint64_t* word_off);
+
+/* Work items (one wave or one workgroup each) the plan gives a table of `keys` keys and
+ * num_bits bits (src/sstable/builder.rs:93 per key): >= 1, non-decreasing in keys.  1: the table's
+ * words are stored once with plain stores; more: its parts OR into a slot cleared first.
+ * For tests and tools, like lsmb_build_strategy.  Measurement switches read at every call
+ * (tools/mb_build_batch.py's geometry A/B): LSMB_BB_WAVE_MAX_BITS (below 65 536: smaller
+ * filters take the workgroup class too) and LSMB_BB_GROUP_LANES (64 .. 1024: that class's
+ * workgroup).  The filter bits never depend on them. */
+int lsmb_build_batch_parts(uint64_t keys, uint32_t num_bits);
+
+/* Device keys (d_offsets == NULL: fixed key_len; else n + 1 uint64_t offsets into d_data), host
+ * seg[ntab + 1], num_bits[ntab], num_hashes[ntab]; d_words: device, 16-byte aligned, words_cap
+ * u64 words.  src/sstable/builder.rs:74,93 for every table of src/compaction/scheduler.rs:147-177's
+ * outputs.  Asynchronous on `stream`, no host synchronisation inside (from the third batch in
+ * flight on one context, the call first waits for the batch two before it: its work list
+ * staging is reused).  LSMB_EINVAL, nothing written: NULL ctx, seg, num_bits, num_hashes or
+ * d_words; NULL keys with a non-empty segment; seg descending or seg[ntab] > n; words_cap <
+ * word_off[ntab]; d_words not 16-byte aligned; num_bits == 0 with num_hashes > 0; a table above
+ * lsmb_build_batch_max_bits() (lsmb_last_error() names the table).  ntab == 0: LSMB_OK, nothing
+ * written. */
+int lsmb_build_batch_dev(lsmb_ctx* ctx, const void* d_data, const void* d_offsets, uint32_t key_len, uint64_t n,
+                         uint64_t ntab, const uint64_t* seg, const uint32_t* num_bits, const uint32_t* num_hashes,
+                         void* d_words, uint64_t words_cap, void* stream);
+
+/* Host keys in, serialized blocks out, synchronous: blocks[block_off[t] .. block_off[t+1]) =
+ * BloomFilter::serialize (src/sstable/builder.rs:177-182) of table t, back to back — the
+ * blocks / block_off form lsmb_lset_add_batch takes.  block_off[ntab + 1] is always filled when
+ * the other arguments pass; blocks == NULL or blocks_cap < block_off[ntab] is then LSMB_EINVAL,
+ * so a first call may ask for the size.  The keys cross once, the packed words come back in one
+ * copy and the host writes the 12-byte headers.  No host fallback: a NULL ctx is LSMB_EINVAL
+ * whatever the key count (src/compaction/scheduler.rs:147-177 batches are the device's).
+ * Other errors as lsmb_build_batch_dev, with blocks and block_off untouched. */
+int lsmb_build_batch_blocks(lsmb_ctx* ctx, const uint8_t* data, const uint64_t* offsets, uint32_t key_len, uint64_t n,
+                            uint64_t ntab, const uint64_t* seg, const uint32_t* num_bits, const uint32_t* num_hashes,
+                            uint8_t* blocks, uint64_t blocks_cap, uint64_t* block_off);
+
 /* CRC-32 of bloom blocks (optional checksum; the reference's
  * bloom block has none).  The same CRC as crc32fast::hash / zlib.crc32, which
  * the store already uses for WAL records and the manifest
@@ -568,6 +628,25 @@ int lsmb_lset_derive(const lsmb_lset* parent, const uint32_t* drop_ids, uint64_t
 int lsmb_lset_add_batch(lsmb_lset* ls, uint64_t ntab, const uint32_t* rows, const uint32_t* table_ids,
                         const uint8_t* blocks, const uint64_t* block_off, const uint32_t* crcs,
                         const uint8_t* keys, const uint64_t* key_off, int32_t* status);
+
+/* ntab tables whose filter words are ALREADY on the set's device, in the packed layout of
+ * lsmb_build_batch_layout (what lsmb_build_batch_dev leaves: the output tables of
+ * src/compaction/scheduler.rs:147-177 pushed into the next Version, their filters finished by
+ * src/sstable/builder.rs:177-182, without a trip through the host): table t goes to rows[t] with
+ * id table_ids[t], its words are the u64 words d_words[word_off[t] ..], its filter is
+ * (num_bits[t], num_hashes[t]), its range as in lsmb_lset_add_batch (keys / key_off).  word_off
+ * must equal that layout for num_bits (LSMB_EINVAL otherwise), d_words must be 16-byte aligned.
+ * Arena slots are reserved as in lsmb_lset_add_batch; the words move in one device-to-device
+ * copy on `stream` (NULL: the context's) per run of tables landing in one arena chunk, followed by
+ * ONE synchronisation of `stream`, so work enqueued on it before the call (the build) is complete
+ * and, on return, d_words is free to go and the set is ready for lsmb_lset_seal.  ALL OR NOTHING
+ * with the undo of lsmb_lset_add_batch; lsmb_last_error() names the first failing index and id.
+ * ntab == 0 is LSMB_OK.  In lsmb_lset_stats these tables count in [0], [4] and [5] and add nothing
+ * to [2] and [3]: no byte crosses PCIe. */
+int lsmb_lset_add_batch_dev(lsmb_lset* ls, uint64_t ntab, const uint32_t* rows, const uint32_t* table_ids,
+                            const void* d_words, const uint64_t* word_off, const uint32_t* num_bits,
+                            const uint32_t* num_hashes, const uint8_t* keys, const uint64_t* key_off,
+                            void* stream);
 
 /* A set's footprint after a chain of version edits (src/compaction/scheduler.rs:163-177):
  * out[0] tables; [1] tables inherited by lsmb_lset_derive; [2] filter bytes this set uploaded;

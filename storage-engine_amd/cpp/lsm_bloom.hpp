@@ -68,6 +68,35 @@ class Context {
         return ctx;
     }
 
+    // Many SSTable filters from one key run (lsmb_build_batch_blocks;
+    // src/sstable/builder.rs:74,93,177-182 for every output table of
+    // src/compaction/scheduler.rs:147-177): table t = BloomFilterBuilder over
+    // keys[seg[t] .. seg[t+1]) in a filter of (num_bits[t], num_hashes[t]);
+    // returns each table's serialized block.  Always on the GPU.
+    std::vector<std::vector<uint8_t>> build_batch_blocks(const std::vector<std::string>& keys,
+                                                         const std::vector<uint64_t>& seg,
+                                                         const std::vector<uint32_t>& num_bits,
+                                                         const std::vector<uint32_t>& num_hashes) {
+        const size_t ntab = num_bits.size();
+        if (seg.size() != ntab + 1 || num_hashes.size() != ntab)
+            throw std::invalid_argument("build_batch_blocks: seg needs ntab + 1 entries, num_hashes ntab");
+        std::vector<uint64_t> offs(keys.size() + 1, 0), boff(ntab + 1, 0);
+        std::string data;
+        for (size_t i = 0; i < keys.size(); i++) {
+            data += keys[i];
+            offs[i + 1] = data.size();
+        }
+        data.push_back('\0');
+        uint64_t total = 0;
+        for (uint32_t nb : num_bits) total += lsmb_serialized_size(nb);
+        std::vector<uint8_t> flat(total + 1);
+        check(lsmb_build_batch_blocks(c_, reinterpret_cast<const uint8_t*>(data.data()), offs.data(), 0, keys.size(), ntab,
+                                      seg.data(), num_bits.data(), num_hashes.data(), flat.data(), total, boff.data()));
+        std::vector<std::vector<uint8_t>> blocks(ntab);
+        for (size_t t = 0; t < ntab; t++) blocks[t].assign(flat.begin() + boff[t], flat.begin() + boff[t + 1]);
+        return blocks;
+    }
+
    private:
     lsmb_ctx* c_ = nullptr;
 };
@@ -319,6 +348,29 @@ class LevelSet {
         check(lsmb_lset_add_batch(ls_, n, rows.data(), table_ids.data(), bb.data(), boff.data(),
                                   crcs ? crcs->data() : nullptr, kb.data(), koff.data(),
                                   status && n ? status->data() : nullptr));
+    }
+    // Tables whose filter words lsmb_build_batch_dev left on this set's device
+    // (lsmb_lset_add_batch_dev): d_words in the layout of
+    // lsmb_build_batch_layout(num_bits).  The words move device to device on
+    // `stream`, which is synchronised once; all or nothing.
+    void add_built(const std::vector<uint32_t>& rows, const std::vector<uint32_t>& table_ids, const void* d_words,
+                   const std::vector<uint32_t>& num_bits, const std::vector<uint32_t>& num_hashes,
+                   const std::vector<TableRange>& ranges, void* stream = nullptr) {
+        const size_t n = ranges.size();
+        if (rows.size() != n || table_ids.size() != n || num_bits.size() != n || num_hashes.size() != n)
+            throw std::invalid_argument("add_built: rows, table_ids, num_bits, num_hashes and ranges differ in length");
+        std::vector<uint64_t> woff(n + 1, 0), koff(2 * n + 1, 0);
+        check(lsmb_build_batch_layout(n, num_bits.data(), woff.data()));
+        std::vector<uint8_t> kb;
+        for (size_t t = 0; t < n; t++) {
+            kb.insert(kb.end(), ranges[t].min_key.begin(), ranges[t].min_key.end());
+            koff[2 * t + 1] = kb.size();
+            kb.insert(kb.end(), ranges[t].max_key.begin(), ranges[t].max_key.end());
+            koff[2 * t + 2] = kb.size();
+        }
+        kb.push_back(0);
+        check(lsmb_lset_add_batch_dev(ls_, n, rows.data(), table_ids.data(), d_words, woff.data(), num_bits.data(),
+                                      num_hashes.data(), kb.data(), koff.data(), stream));
     }
     // lsmb_lset_stats: [0] tables, [1] inherited by derive, [2] filter bytes
     // and [3] copy calls of this set's own uploads, [4] device bytes of the

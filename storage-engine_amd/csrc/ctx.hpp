@@ -127,6 +127,22 @@ struct lsmb_ctx {
     uint8_t* pin_small = nullptr;  // pinned staging of small host builds (host_build_small)
     uint64_t pin_small_cap = 0;
     lsmb::PinnedPool pinned_retired;  // outgrown pinned staging, freed by lsmb_close
+    // batched builds (lsmb_build_batch_*): the work list crosses through one of
+    // two pinned staging slots into that slot's device copy, one async copy on
+    // the caller's stream.  bb_done[s] is completed by the last launch of the
+    // slot's last batch: the host waits for it before refilling the slot (two
+    // batches later), and a batch on another stream waits for it before its
+    // copy overwrites the device items, the way a build waits on ws_done.
+    uint8_t* bb_pin[2] = {nullptr, nullptr};
+    uint64_t bb_pin_cap[2] = {0, 0};
+    lsmb::DevBuf bb_items[2];
+    hipEvent_t bb_done[2] = {nullptr, nullptr};
+    hipStream_t bb_stream[2] = {nullptr, nullptr};  // stream of the slot's last batch (nullptr: none yet)
+    int bb_slot = 0;
+    // lsmb_build_batch_blocks: the packed words on the device and, pinned, back on the host
+    lsmb::DevBuf bb_words;
+    uint8_t* bb_host = nullptr;
+    uint64_t bb_host_cap = 0;
 };
 
 namespace lsmb {

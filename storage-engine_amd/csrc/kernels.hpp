@@ -144,6 +144,18 @@ hipError_t launch_build(const KeyBatch& kb, uint32_t num_bits, uint32_t k, uint3
                         hipStream_t st, BuildTimers* timers, int sweep = -1, bool fresh = false,
                         hipEvent_t done = nullptr);  // done: completed by the build's last kernel (launch_done)
 
+// The batched build (build_batch.hip; plan, layout and item format in
+// build_batch_plan.hpp): d_items holds nzero zero-pass items, then nwave wave
+// items, then ngroup group items (device memory, read by the launches on st);
+// *_region32 = the u32 words of the largest slot of each class, group_lanes =
+// the group class's workgroup (kBbGroupLanes; fewer only to measure).  Writes the
+// slots those items name inside d_words (16-byte aligned) and nothing else.
+// done (optional): completed by the last launch.  No host synchronisation.
+struct BbItem;
+hipError_t launch_build_batch(const KeyBatch& kb, const BbItem* d_items, uint32_t nzero, uint32_t nwave,
+                              uint32_t ngroup, uint32_t wave_region32, uint32_t group_region32, uint32_t group_lanes,
+                              uint64_t* d_words, hipStream_t st, hipEvent_t done = nullptr);
+
 // Filter descriptor for the probe kernels (device-side array).
 struct ProbeFilter {
     const uint32_t* words32;

@@ -107,6 +107,7 @@ SIGNATURES = {
     "lsmb_lset_derive": (ctypes.c_int, [vp, u32p, ctypes.c_uint64, u64p, ctypes.POINTER(vp)]),
     "lsmb_lset_add_batch": (ctypes.c_int, [vp, ctypes.c_uint64, u32p, u32p, u8p, u64p, u32p, u8p, u64p,
                                            ctypes.POINTER(ctypes.c_int32)]),
+    "lsmb_lset_add_batch_dev": (ctypes.c_int, [vp, ctypes.c_uint64, u32p, u32p, vp, u64p, u32p, u32p, u8p, u64p, vp]),
     "lsmb_lset_stats": (ctypes.c_int, [vp, u64p]),
     "lsmb_lset_rows": (ctypes.c_int, [vp]),
     "lsmb_lset_tables": (ctypes.c_uint64, [vp, ctypes.c_uint32]),
@@ -128,6 +129,13 @@ SIGNATURES = {
     "lsmb_build_fixed_dev_sweep_new": (ctypes.c_int, [vp, vp, ctypes.c_uint32, ctypes.c_uint64, ctypes.c_uint32,
                                                       ctypes.c_uint32, vp, ctypes.c_int, vp]),
     "lsmb_set_host_max_keys": (None, [ctypes.c_uint64]),
+    "lsmb_build_batch_max_bits": (ctypes.c_uint32, []),
+    "lsmb_build_batch_layout": (ctypes.c_int, [ctypes.c_uint64, u32p, u64p]),
+    "lsmb_build_batch_parts": (ctypes.c_int, [ctypes.c_uint64, ctypes.c_uint32]),
+    "lsmb_build_batch_dev": (ctypes.c_int, [vp, vp, vp, ctypes.c_uint32, ctypes.c_uint64, ctypes.c_uint64, u64p, u32p,
+                                            u32p, vp, ctypes.c_uint64, vp]),
+    "lsmb_build_batch_blocks": (ctypes.c_int, [vp, u8p, u64p, ctypes.c_uint32, ctypes.c_uint64, ctypes.c_uint64, u64p,
+                                               u32p, u32p, u8p, ctypes.c_uint64, u64p]),
     "lsmb_multi_open": (ctypes.c_int, [ctypes.POINTER(vp), ctypes.POINTER(ctypes.c_int), ctypes.c_int]),
     "lsmb_multi_close": (None, [vp]),
     "lsmb_multi_size": (ctypes.c_int, [vp]),
@@ -406,6 +414,54 @@ class Context:
     def build_var_dev_new(self, data, offsets, n, num_bits, k, words, stream=None):
         _check(lib().lsmb_build_var_dev_new(self.h, vp(data.data_ptr()), vp(offsets.data_ptr() if n else 0), n,
                                             num_bits, k, vp(words.data_ptr()), self._stream(stream)))
+
+    # Many SSTable filters from one key run (src/sstable/builder.rs:74,93,177-182
+    # for every output table of src/compaction/scheduler.rs:147-177): table t =
+    # BloomFilter::new + insert of keys [seg[t], seg[t+1]) of the run.
+    def build_batch_dev(self, data, n, seg, num_bits, num_hashes, words, offsets=None, key_len=0, stream=None):
+        """lsmb_build_batch_dev: data (and offsets, n + 1 int64, for var-len
+        keys) device tensors; seg (ntab + 1), num_bits and num_hashes (ntab)
+        host sequences; words a 16-byte-aligned int64 device tensor of at least
+        build_batch_layout(num_bits)[-1] words, output-only, in that layout.
+        Asynchronous on stream.  Returns the layout (word_off, uint64)."""
+        seg = np.ascontiguousarray(seg, dtype=np.uint64)
+        nb = np.ascontiguousarray(num_bits, dtype=np.uint32)
+        kk = np.ascontiguousarray(num_hashes, dtype=np.uint32)
+        ntab = nb.size
+        if seg.size != ntab + 1 or kk.size != ntab:
+            raise ValueError("build_batch_dev: seg needs ntab + 1 entries, num_hashes ntab")
+        _check(lib().lsmb_build_batch_dev(self.h, vp(data.data_ptr()) if data is not None else None,
+                                          vp(offsets.data_ptr()) if offsets is not None else None, key_len, int(n),
+                                          ntab, _p(seg, u64p), _p(nb, u32p) if ntab else None,
+                                          _p(kk, u32p) if ntab else None, vp(words.data_ptr()),
+                                          words.numel() * words.element_size() // 8, self._stream(stream)))
+        return build_batch_layout(nb)
+
+    def build_batch_blocks(self, data, seg, num_bits, num_hashes, offsets=None, key_len=0):
+        """lsmb_build_batch_blocks: packed host keys (as build_block) ->
+        (blocks, block_off): the tables' serialized bloom blocks back to back
+        (uint8) and their ntab + 1 offsets (uint64), the form
+        lsmb_lset_add_batch takes.  Runs on the GPU whatever the key count."""
+        data = np.ascontiguousarray(data, dtype=np.uint8).reshape(-1)
+        if offsets is not None:
+            offsets = np.ascontiguousarray(offsets, dtype=np.uint64)
+            n, op = offsets.size - 1, _p(offsets, u64p)
+        else:
+            n, op = (data.size // key_len if key_len else 0), None
+        seg = np.ascontiguousarray(seg, dtype=np.uint64)
+        nb = np.ascontiguousarray(num_bits, dtype=np.uint32)
+        kk = np.ascontiguousarray(num_hashes, dtype=np.uint32)
+        ntab = nb.size
+        if seg.size != ntab + 1 or kk.size != ntab:
+            raise ValueError("build_batch_blocks: seg needs ntab + 1 entries, num_hashes ntab")
+        boff = np.zeros(ntab + 1, dtype=np.uint64)
+        blocks = np.empty(max(sum(serialized_size(int(b)) for b in nb), 1), dtype=np.uint8)
+        if data.size == 0:
+            data = np.zeros(1, np.uint8)
+        _check(lib().lsmb_build_batch_blocks(self.h, _p(data, u8p), op, key_len, n, ntab, _p(seg, u64p),
+                                             _p(nb, u32p) if ntab else None, _p(kk, u32p) if ntab else None,
+                                             _p(blocks, u8p), blocks.size, _p(boff, u64p)))
+        return blocks[:int(boff[ntab])], boff
 
     def probe_dev(self, filters, data, n, out, offsets=None, key_len=0, stream=None):
         """filters: [(words tensor on device, num_bits, k)]."""
@@ -789,6 +845,32 @@ class LevelSet:
             raise
         return status[:n]
 
+    def add_built(self, rows, ids, words, num_bits, num_hashes, ranges, stream=None):
+        """Tables whose filters Context.build_batch_dev left on this set's
+        device (lsmb_lset_add_batch_dev): words the int64 device tensor in the
+        layout of build_batch_layout(num_bits), rows / ids / num_bits /
+        num_hashes per table, ranges a list of (min_key, max_key).  The words
+        move device to device on stream, which is synchronised once: on return
+        `words` is free and the set is ready for seal.  All or nothing."""
+        n = len(ranges)
+        rows = np.ascontiguousarray(rows, dtype=np.uint32)
+        ids = np.ascontiguousarray(ids, dtype=np.uint32)
+        nb = np.ascontiguousarray(num_bits, dtype=np.uint32)
+        kk = np.ascontiguousarray(num_hashes, dtype=np.uint32)
+        if not (rows.size == ids.size == nb.size == kk.size == n):
+            raise ValueError("add_built: rows, ids, num_bits, num_hashes and ranges differ in length")
+        woff = build_batch_layout(nb)
+        if words.numel() * words.element_size() < 8 * int(woff[n]):
+            raise ValueError("add_built: words is smaller than the layout of num_bits")
+        flat = [bytes(k) for lo_hi in ranges for k in lo_hi]
+        koff = np.zeros(2 * n + 1, dtype=np.uint64)
+        np.cumsum([len(k) for k in flat], out=koff[1:])
+        kb = np.frombuffer(b"".join(flat) + b"\0", dtype=np.uint8)
+        _check(lib().lsmb_lset_add_batch_dev(self.h, n, _p(rows, u32p) if n else None, _p(ids, u32p) if n else None,
+                                             vp(words.data_ptr()), _p(woff, u64p), _p(nb, u32p) if n else None,
+                                             _p(kk, u32p) if n else None, _p(kb, u8p), _p(koff, u64p),
+                                             Context._stream(stream)))
+
     def stats(self):
         """lsmb_lset_stats: tables, inherited (by derive), uploaded_bytes and
         upload_copies (this set's own filter uploads), chunk_bytes (device
@@ -908,6 +990,26 @@ class LevelSet:
 def build_strategy(num_bits, n, k=7):
     """Device build strategy for (num_bits, k, n): lds / tiled / partition / atomic."""
     return lib().lsmb_build_strategy(num_bits, k, n).decode()
+
+
+def build_batch_max_bits():
+    """Largest num_bits a table of a batched build may have (lsmb_build_batch_max_bits)."""
+    return int(lib().lsmb_build_batch_max_bits())
+
+
+def build_batch_layout(num_bits):
+    """Packed layout of a batched build (lsmb_build_batch_layout): word_off,
+    uint64 of len(num_bits) + 1; table t's u64 words start at word_off[t],
+    word_off[-1] is the words of the whole buffer."""
+    nb = np.ascontiguousarray(num_bits, dtype=np.uint32)
+    woff = np.zeros(nb.size + 1, dtype=np.uint64)
+    _check(lib().lsmb_build_batch_layout(nb.size, _p(nb, u32p) if nb.size else None, _p(woff, u64p)))
+    return woff
+
+
+def build_batch_parts(keys, num_bits):
+    """Work items a batched build gives one table of this shape (lsmb_build_batch_parts)."""
+    return int(lib().lsmb_build_batch_parts(int(keys), int(num_bits)))
 
 
 def crc32(data, crc=0):
