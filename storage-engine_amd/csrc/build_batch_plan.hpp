@@ -14,18 +14,16 @@
 #include <vector>
 
 #include "bloom_math.hpp"
+#include "lset_arena.hpp"
 
 namespace lsmb {
 
 // ---- the packed layout -------------------------------------------------------
 // Table t's u64 words start at word_off[t]; its slot is max(ceil(num_bits/64), 1)
 // words rounded up to an even count: 16-byte-aligned slots, the arena's own rule
-// (lset_slot_bytes in capi.hip), so a packed buffer and the arena agree slot for
-// slot and a run of slots moves into a chunk as one copy.
-inline uint64_t bb_slot_words(uint32_t num_bits) {
-    const uint64_t nw = ((uint64_t)num_bits + 63) / 64;
-    return (std::max<uint64_t>(nw, 1) + 1) & ~(uint64_t)1;
-}
+// (lset_slot_bytes in lset_arena.hpp), so a packed buffer and the arena agree slot
+// for slot and a run of slots moves into a chunk as one copy.
+inline uint64_t bb_slot_words(uint32_t num_bits) { return lset_slot_bytes(((uint64_t)num_bits + 63) / 64) / 8; }
 
 // word_off[0 .. ntab]; word_off[ntab] = the words of the whole buffer.
 inline void bb_layout(uint64_t ntab, const uint32_t* num_bits, uint64_t* word_off) {

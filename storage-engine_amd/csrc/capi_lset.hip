@@ -1,0 +1,684 @@
+// capi_lset.hip — the C ABI of the level set (lsmb_lset_*, include/lsmbloom.h).
+// Host-side plumbing only; the placement of filters in the arena is planned in
+// lset_arena.hpp, the kernels are in lset.hip, lset_lists.hip and crc32.hip.
+#include <string.h>
+
+#include <algorithm>
+#include <memory>
+#include <string>
+#include <vector>
+
+#include "crc_seg.hpp"
+#include "ctx.hpp"
+#include "lset_arena.hpp"
+#include "lset_lists_plan.hpp"
+#include "lset_order.hpp"
+
+using namespace lsmb;
+
+extern "C" {
+
+// ---------------------------------------------------------------- level sets
+// An immutable, device-resident snapshot of the store's non-overlapping
+// levels (one per Version, src/db/mod.rs:255-267): rows of tables with
+// pairwise disjoint key ranges, any number per row.  Tables are added in any
+// order, each filter copied into a device arena as it arrives; seal sorts the
+// rows, checks them (lset_order.hpp) and uploads the descriptors.  A sealed
+// set is only read, so its probes need no scratch and no ordering.
+//
+// A Version edit (src/compaction/scheduler.rs:163-177) derives the next set
+// from a sealed one: the child holds the surviving tables with their device
+// words where they are, so the arena chunks are reference-counted (the counts
+// are shared_ptr's, atomic: a parent may be probed while a child is derived)
+// and a chunk goes when the last set holding one of its tables is closed.  A
+// set bump-allocates only in chunks it allocated itself (own_tail), never in
+// the tail of an inherited one: two children of one parent would collide
+// there, and a sealed set's memory stays read-only for probes in flight.
+namespace lsmb {
+struct LsetChunk {
+    int dev = 0;
+    DevBuf buf;
+    ~LsetChunk() {  // the last set holding the chunk closes (or a failed add gives its chunks back)
+        DevGuard g(dev);
+        buf.release();
+    }
+};
+
+// Steps 2 and 3 of an add (below): where the filters go, and the chunks that
+// do not exist yet.
+struct LsetStaged {
+    LsetPlacement pl;
+    std::vector<std::shared_ptr<LsetChunk>> fresh;  // pl.new_chunks, allocated
+    std::vector<uint8_t*> words;                    // per table: the device address of its slot
+};
+}  // namespace lsmb
+
+struct lsmb_lset {
+    lsmb_ctx* c = nullptr;
+    struct Table {
+        uint32_t id = 0, num_bits = 0, k = 0;
+        uint32_t chunk = 0;               // index into chunks
+        const uint32_t* words = nullptr;  // in the arena
+        std::vector<uint8_t> lo, hi;
+    };
+    std::vector<Table> row[kLsetMaxRows];
+    uint32_t nrows = 0;  // 1 + highest row added
+    bool sealed = false;
+    // filter words: bump-allocated from chunks that are never reallocated;
+    // a derived set's inherited chunks come first.  arena is the bump state
+    // over them (lset_arena.hpp), arena.chunks == chunks.size()
+    std::vector<std::shared_ptr<LsetChunk>> chunks;
+    LsetArenaState arena;
+    // the add in progress; between adds it holds nothing but its vectors'
+    // capacity, so that a loop of single adds does not allocate for each
+    LsetStaged staged;
+    // lsmb_lset_stats: tables taken over by derive, filter bytes and copy calls of this set's uploads
+    uint64_t inherited = 0, up_bytes = 0, up_copies = 0;
+    // lsmb_lset_add_batch: pinned staging (words in the arena's layout, CRC
+    // segments and results) and the device side of the CRC check
+    uint8_t* pin = nullptr;
+    uint64_t pin_cap = 0;
+    PinnedPool pin_retired;
+    DevBuf segs;
+    DevBuf bounds, desc, pfx;  // seal: the bound keys' bytes, LsetTable[], prefix pairs
+    LsetRows rows{};
+    // seal: the table id of every ordinal (row by row, each in its sealed
+    // order) and the first ordinal of every row, base[nrows] = all tables
+    std::vector<uint32_t> ids;
+    uint64_t base[kLsetMaxRows + 1] = {0};
+    hipStream_t ust = nullptr;  // uploads
+};
+
+namespace {
+
+// Every add (lset_add_common, lsmb_lset_add_batch, lsmb_lset_add_batch_dev)
+// runs the same five steps: the host checks, the placement (lset_place), this
+// call's new chunks, the copies and their wait, the commit.  The set is not
+// touched before the commit (ls->staged is the add's own scratch), so a refused
+// or failed add has nothing to undo.
+
+// Device address of byte `off` of chunk `chunk`: one of the set's, or one of
+// the staged add's new chunks after them.
+uint8_t* lset_at(const lsmb_lset* ls, uint32_t chunk, size_t off) {
+    const size_t held = ls->chunks.size();
+    return (uint8_t*)(chunk < held ? ls->chunks[chunk] : ls->staged.fresh[chunk - held])->buf.p + off;
+}
+
+// Steps 2 and 3 into ls->staged.
+int lset_stage(lsmb_lset* ls, const uint64_t* nw, uint64_t ntab) {
+    LsetStaged& sg = ls->staged;
+    if (!lset_place(ls->arena, nw, ntab, &sg.pl)) return fail(LSMB_EINVAL, "level set arena is full");
+    for (const size_t bytes : sg.pl.new_chunks) {
+        auto ch = std::make_shared<LsetChunk>();
+        ch->dev = ls->c->dev;
+        const hipError_t e = ch->buf.ensure(bytes);
+        if (e != hipSuccess) return hip_fail(e, "ch->buf.ensure(std::max(bytes, kLsetChunkBytes))");
+        sg.fresh.push_back(std::move(ch));
+    }
+    sg.words.resize(ntab);
+    for (uint64_t t = 0; t < ntab; t++) sg.words[t] = lset_at(ls, sg.pl.slot[t].chunk, sg.pl.slot[t].off);
+    return LSMB_OK;
+}
+
+// A failed add gives its chunks back: the stream first (~LsetChunk frees, and a
+// copy may still be in flight), last_error() kept across the wait.
+int lset_abandon(lsmb_lset* ls, hipStream_t st, int rc) {
+    const std::string msg = last_error();
+    (void)hipStreamSynchronize(st);
+    ls->staged.fresh.clear();
+    set_last_error(msg);
+    return rc;
+}
+
+// Step 5, after every copy has completed: the new chunks, the bump state, the
+// tables (tabs[t] into rows[t], its slot from the placement) and the stats.
+void lset_commit(lsmb_lset* ls, const uint32_t* rows, lsmb_lset::Table* tabs, uint64_t ntab, uint64_t up_bytes,
+                 uint64_t up_copies) {
+    LsetStaged& sg = ls->staged;
+    for (auto& ch : sg.fresh) ls->chunks.push_back(std::move(ch));
+    sg.fresh.clear();
+    ls->arena = sg.pl.after;
+    for (uint64_t t = 0; t < ntab; t++) {
+        tabs[t].chunk = sg.pl.slot[t].chunk;
+        tabs[t].words = (const uint32_t*)sg.words[t];
+        ls->row[rows[t]].push_back(std::move(tabs[t]));
+        ls->nrows = std::max(ls->nrows, rows[t] + 1);
+    }
+    ls->up_bytes += up_bytes;
+    ls->up_copies += up_copies;
+}
+
+// A table's key range as every add checks it.
+int lset_range_check(const uint8_t* min_key, uint64_t min_len, const uint8_t* max_key, uint64_t max_len) {
+    if ((min_len && !min_key) || (max_len && !max_key)) return fail(LSMB_EINVAL, "null key range");
+    if (min_len > UINT32_MAX || max_len > UINT32_MAX) return fail(LSMB_EINVAL, "range key too long");
+    return LSMB_OK;
+}
+
+int lset_add_common(lsmb_lset* ls, uint32_t row, uint32_t table_id, const uint8_t* words_le, uint32_t num_bits,
+                    uint32_t k, const uint8_t* min_key, uint64_t min_len, const uint8_t* max_key, uint64_t max_len) {
+    if (int rc = check_filter(num_bits, k)) return rc;
+    if (int rc = lset_range_check(min_key, min_len, max_key, max_len)) return rc;
+    if (ls->row[row].size() >= UINT32_MAX) return fail(LSMB_EINVAL, "level set row %u is full", row);
+    DevGuard g(ls->c->dev);
+    const uint64_t nw = nwords64(num_bits);
+    lsmb_lset::Table tab;
+    tab.id = table_id;
+    tab.num_bits = num_bits;
+    tab.k = k;
+    tab.lo.assign(min_key, min_key + min_len);
+    tab.hi.assign(max_key, max_key + max_len);
+    auto upload = [&]() -> int {
+        if (int rc = lset_stage(ls, &nw, 1)) return rc;
+        if (nw) {
+            HIP_TRY(hipMemcpyAsync(ls->staged.words[0], words_le, nw * 8, hipMemcpyHostToDevice, ls->ust));
+            HIP_TRY(hipStreamSynchronize(ls->ust));  // the caller's block is free to go
+        }
+        return LSMB_OK;
+    };
+    if (int rc = upload()) return lset_abandon(ls, ls->ust, rc);
+    lset_commit(ls, &row, &tab, 1, nw * 8, nw ? 1 : 0);
+    return LSMB_OK;
+}
+
+int lset_add_check(const lsmb_lset* ls, uint32_t row, uint32_t table_id) {
+    if (!ls) return fail(LSMB_EINVAL, "null level set");
+    if (ls->sealed) return fail(LSMB_EINVAL, "level set is sealed: a new Version takes a new set");
+    if (row >= kLsetMaxRows) return fail(LSMB_EINVAL, "row %u: a level set has %u rows", row, kLsetMaxRows);
+    if (table_id == LSMB_LSET_NONE) return fail(LSMB_EINVAL, "table id 0xFFFFFFFF is the probe's 'no table' answer");
+    return LSMB_OK;
+}
+
+int lset_probe_check(const lsmb_lset* ls) {
+    if (!ls) return fail(LSMB_EINVAL, "null level set");
+    if (!ls->sealed) return fail(LSMB_EINVAL, "level set not sealed");
+    return LSMB_OK;
+}
+
+}  // namespace
+
+int lsmb_lset_open(lsmb_ctx* c, lsmb_lset** out) {
+    if (!c || !out) return fail(LSMB_EINVAL, "null argument");
+    *out = nullptr;
+    DevGuard g(c->dev);
+    lsmb_lset* ls = new lsmb_lset;
+    ls->c = c;
+    if (hipStreamCreateWithFlags(&ls->ust, hipStreamNonBlocking) != hipSuccess) {
+        delete ls;
+        return fail(LSMB_EHIP, "level set: stream creation failed");
+    }
+    *out = ls;
+    return LSMB_OK;
+}
+
+void lsmb_lset_close(lsmb_lset* ls) {
+    if (!ls) return;
+    {
+        DevGuard g(ls->c->dev);
+        if (ls->ust) hipStreamSynchronize(ls->ust), hipStreamDestroy(ls->ust);
+        ls->chunks.clear();  // each chunk goes with the last set holding it
+        ls->segs.release();
+        if (ls->pin) (void)hipHostFree(ls->pin);  // teardown
+        ls->pin_retired.release();
+        ls->bounds.release();
+        ls->desc.release();
+        ls->pfx.release();
+    }
+    delete ls;
+}
+
+int lsmb_lset_add(lsmb_lset* ls, uint32_t row, uint32_t table_id, const uint8_t* block, uint64_t len,
+                  const uint8_t* min_key, uint64_t min_len, const uint8_t* max_key, uint64_t max_len) {
+    if (int rc = lset_add_check(ls, row, table_id)) return rc;
+    uint32_t k, nb, nw;
+    if (int rc = lsmb_deserialize_header(block, len, &k, &nb, &nw)) return rc;
+    return lset_add_common(ls, row, table_id, block + 12, nb, k, min_key, min_len, max_key, max_len);
+}
+
+int lsmb_lset_add_words(lsmb_lset* ls, uint32_t row, uint32_t table_id, const uint64_t* words, uint32_t num_bits,
+                        uint32_t num_hashes, const uint8_t* min_key, uint64_t min_len, const uint8_t* max_key,
+                        uint64_t max_len) {
+    if (int rc = lset_add_check(ls, row, table_id)) return rc;
+    if (!words && nwords64(num_bits)) return fail(LSMB_EINVAL, "null words");
+    return lset_add_common(ls, row, table_id, (const uint8_t*)words, num_bits, num_hashes, min_key, min_len, max_key,
+                           max_len);
+}
+
+int lsmb_lset_derive(const lsmb_lset* parent, const uint32_t* drop_ids, uint64_t ndrop, uint64_t* dropped,
+                     lsmb_lset** out) {
+    if (out) *out = nullptr;
+    if (!parent || !out) return fail(LSMB_EINVAL, "null argument");
+    if (!parent->sealed) return fail(LSMB_EINVAL, "derive from an unsealed level set");
+    if (ndrop && !drop_ids) return fail(LSMB_EINVAL, "null drop_ids");
+    std::vector<uint32_t> drop(drop_ids, drop_ids + ndrop);
+    std::sort(drop.begin(), drop.end());
+    lsmb_lset* ls = nullptr;
+    if (int rc = lsmb_lset_open(parent->c, &ls)) return rc;
+    // the surviving tables, each in its row, and only the chunks that hold one
+    std::vector<uint32_t> remap(parent->chunks.size(), UINT32_MAX);
+    uint64_t nd = 0;
+    for (uint32_t r = 0; r < parent->nrows; r++)
+        for (const auto& T : parent->row[r]) {
+            if (std::binary_search(drop.begin(), drop.end(), T.id)) {
+                nd++;
+                continue;
+            }
+            if (remap[T.chunk] == UINT32_MAX) {
+                remap[T.chunk] = (uint32_t)ls->chunks.size();
+                ls->chunks.push_back(parent->chunks[T.chunk]);
+            }
+            ls->row[r].push_back(T);
+            ls->row[r].back().chunk = remap[T.chunk];
+            ls->inherited++;
+        }
+    ls->arena.chunks = ls->chunks.size();  // none of them the child's own: its first add takes a new chunk
+    ls->nrows = parent->nrows;
+    if (dropped) *dropped = nd;
+    *out = ls;
+    return LSMB_OK;
+}
+
+namespace {
+
+// Table t of a batch, its bounds at ko[0 .. 2] in keys; its slot comes with the commit.
+void lset_batch_table(lsmb_lset::Table* T, uint32_t id, uint32_t num_bits, uint32_t k, const uint8_t* keys,
+                      const uint64_t* ko) {
+    T->id = id;
+    T->num_bits = num_bits;
+    T->k = k;
+    if (ko[1] > ko[0]) T->lo.assign(keys + ko[0], keys + ko[1]);
+    if (ko[2] > ko[1]) T->hi.assign(keys + ko[1], keys + ko[2]);
+}
+
+// What both batches check of a table once its filter is known.
+int lset_batch_table_check(const lsmb_lset* ls, uint64_t ntab, uint32_t row, uint32_t num_bits, uint32_t k,
+                           const uint8_t* keys, const uint64_t* koff) {
+    if (int rc = check_filter(num_bits, k)) return rc;
+    if (koff[1] < koff[0] || koff[2] < koff[1]) return fail(LSMB_EINVAL, "key offsets descend");
+    if (int rc = lset_range_check(keys, koff[1] - koff[0], keys, koff[2] - koff[1])) return rc;
+    if (ls->row[row].size() + ntab >= UINT32_MAX) return fail(LSMB_EINVAL, "level set row %u is full", row);
+    return LSMB_OK;
+}
+
+// One table of lsmb_lset_add_batch: its host-side checks, then *T.
+int lset_batch_check_one(const lsmb_lset* ls, uint64_t ntab, uint32_t row, uint32_t id, const uint8_t* blocks,
+                         const uint64_t* boff, const uint8_t* keys, const uint64_t* koff, lsmb_lset::Table* T) {
+    if (int rc = lset_add_check(ls, row, id)) return rc;
+    if (boff[1] < boff[0]) return fail(LSMB_EINVAL, "block offsets descend");
+    uint32_t k = 0, nb = 0, nw32 = 0;
+    if (int rc = lsmb_deserialize_header(blocks ? blocks + boff[0] : nullptr, boff[1] - boff[0], &k, &nb, &nw32))
+        return rc;
+    if (int rc = lset_batch_table_check(ls, ntab, row, nb, k, keys, koff)) return rc;
+    lset_batch_table(T, id, nb, k, keys, koff);
+    return LSMB_OK;
+}
+
+// Slots, staging, copies and the CRC check of a batch whose headers passed
+// (nw[t]: table t's u64 words).
+int lset_batch_upload(lsmb_lset* ls, uint64_t ntab, const uint64_t* nw, const uint32_t* ids, const uint8_t* blocks,
+                      const uint64_t* boff, const uint32_t* crcs, int32_t* status) {
+    // slots in the arena, 16-B aligned, and the runs they form per chunk
+    if (int rc = lset_stage(ls, nw, ntab)) return rc;
+    const LsetStaged* sg = &ls->staged;
+    const size_t stage = sg->pl.packed_bytes();
+    // the CRC segments (up to 128 KiB each: one wave per segment) and their results after the words
+    std::vector<uint64_t> seg_of;
+    if (crcs)
+        for (uint64_t t = 0; t < ntab; t++)
+            if (nw[t] * 8 <= kCrcSegWaveMax) seg_of.push_back(t);
+    const size_t nseg = seg_of.size();
+    const size_t seg_at = stage, out_at = seg_at + nseg * sizeof(CrcSeg);
+    if (int rc = pinned_ensure(ls->pin_retired, &ls->pin, &ls->pin_cap, out_at + nseg * 4 + 16, "level set")) return rc;
+    size_t at = 0;  // table t's words in the pinned staging: the slots back to back
+    for (uint64_t t = 0; t < ntab; t++) {
+        const size_t slot = lset_slot_bytes(nw[t]);
+        if (nw[t]) memcpy(ls->pin + at, blocks + boff[t] + 12, nw[t] * 8);
+        memset(ls->pin + at + nw[t] * 8, 0, slot - nw[t] * 8);
+        at += slot;
+    }
+    for (const LsetSpan& sp : sg->pl.spans)  // one copy per chunk touched
+        HIP_TRY(hipMemcpyAsync(lset_at(ls, sp.chunk, sp.off), ls->pin + sp.src, sp.bytes, hipMemcpyHostToDevice, ls->ust));
+    if (nseg) {
+        CrcSeg* hs = (CrcSeg*)(ls->pin + seg_at);
+        for (size_t s = 0; s < nseg; s++) hs[s] = CrcSeg{sg->words[seg_of[s]], nw[seg_of[s]] * 8};
+        HIP_TRY(ls->segs.ensure(nseg * (sizeof(CrcSeg) + 4)));
+        uint8_t* ds = (uint8_t*)ls->segs.p;
+        uint32_t* dout = (uint32_t*)(ds + nseg * sizeof(CrcSeg));
+        HIP_TRY(hipMemcpyAsync(ds, hs, nseg * sizeof(CrcSeg), hipMemcpyHostToDevice, ls->ust));
+        if (int rc = crc32_seg_dev((const CrcSeg*)ds, nseg, dout, ls->ust)) return rc;
+        HIP_TRY(hipMemcpyAsync(ls->pin + out_at, dout, nseg * 4, hipMemcpyDeviceToHost, ls->ust));
+    }
+    HIP_TRY(hipStreamSynchronize(ls->ust));  // the batch's one wait: the caller's blocks are free to go
+    if (!crcs) return LSMB_OK;
+    // the copies now in HBM, not the host bytes, are what probes will read
+    std::vector<uint32_t> words_crc(ntab, 0);
+    const uint32_t* hout = (const uint32_t*)(ls->pin + out_at);
+    for (size_t s = 0; s < nseg; s++) words_crc[seg_of[s]] = hout[s];
+    for (uint64_t t = 0; t < ntab; t++)
+        if (nw[t] * 8 > kCrcSegWaveMax)
+            if (int rc = crc32_dev(ls->c, sg->words[t], nw[t] * 8, 0, ls->ust, &words_crc[t])) return rc;
+    int first = LSMB_OK;
+    uint64_t f_len = 0;
+    uint32_t f = 1u << 31;  // x^(8·f_len): the tables of a store mostly share one size
+    for (uint64_t t = 0; t < ntab; t++) {
+        if (nw[t] * 8 != f_len) f = x8nmodp(f_len = nw[t] * 8);
+        const uint32_t got = multmodp(f, crc32_host(blocks + boff[t], 12, 0)) ^ words_crc[t];  // header ‖ words
+        if (got == crcs[t]) continue;
+        if (status) status[t] = LSMB_ECORRUPT;
+        if (first == LSMB_OK)
+            first = fail(LSMB_ECORRUPT,
+                         "table %llu of the batch (id %u): bloom block CRC-32 mismatch: expected %08x, device copy %08x",
+                         (unsigned long long)t, ids[t], crcs[t], got);
+    }
+    return first;
+}
+
+}  // namespace
+
+int lsmb_lset_add_batch(lsmb_lset* ls, uint64_t ntab, const uint32_t* rows, const uint32_t* table_ids,
+                        const uint8_t* blocks, const uint64_t* block_off, const uint32_t* crcs, const uint8_t* keys,
+                        const uint64_t* key_off, int32_t* status) {
+    if (!ls) return fail(LSMB_EINVAL, "null level set");
+    if (ls->sealed) return fail(LSMB_EINVAL, "level set is sealed: a new Version takes a new set");
+    if (ntab == 0) return LSMB_OK;
+    if (!rows || !table_ids || !block_off || !key_off) return fail(LSMB_EINVAL, "null argument");
+    if (ntab >= UINT32_MAX) return fail(LSMB_EINVAL, "more than 2^32-2 tables in one batch");
+    // every header on the host first: nothing is allocated or uploaded for a batch that fails here
+    std::vector<lsmb_lset::Table> tabs(ntab);
+    int first_rc = LSMB_OK;
+    uint64_t first_t = 0;
+    std::string first_msg;
+    for (uint64_t t = 0; t < ntab; t++) {
+        const int rc = lset_batch_check_one(ls, ntab, rows[t], table_ids[t], blocks, block_off + t, keys,
+                                            key_off + 2 * t, &tabs[t]);
+        if (status) status[t] = rc;
+        if (rc && first_rc == LSMB_OK) {
+            first_rc = rc;
+            first_t = t;
+            first_msg = last_error();
+        }
+    }
+    if (first_rc)
+        return fail(first_rc, "table %llu of the batch (id %u): %s", (unsigned long long)first_t, table_ids[first_t],
+                    first_msg.c_str());
+    DevGuard g(ls->c->dev);
+    std::vector<uint64_t> nw(ntab);
+    uint64_t up_bytes = 0;
+    for (uint64_t t = 0; t < ntab; t++) up_bytes += (nw[t] = nwords64(tabs[t].num_bits)) * 8;
+    if (int rc = lset_batch_upload(ls, ntab, nw.data(), table_ids, blocks, block_off, crcs, status))
+        return lset_abandon(ls, ls->ust, rc);  // all or nothing
+    lset_commit(ls, rows, tabs.data(), ntab, up_bytes, ls->staged.pl.spans.size());
+    return LSMB_OK;
+}
+
+// Filters a batched build left on the set's device (lsmb_build_batch_dev: the
+// outputs of src/compaction/scheduler.rs:147-177 pushed into the next Version
+// without a trip through the host): the slots of the packed buffer are the
+// arena's slots, so each run of tables landing in one chunk is one
+// device-to-device copy.
+int lsmb_lset_add_batch_dev(lsmb_lset* ls, uint64_t ntab, const uint32_t* rows, const uint32_t* table_ids,
+                            const void* d_words, const uint64_t* word_off, const uint32_t* num_bits,
+                            const uint32_t* num_hashes, const uint8_t* keys, const uint64_t* key_off, void* stream) {
+    if (!ls) return fail(LSMB_EINVAL, "null level set");
+    if (ls->sealed) return fail(LSMB_EINVAL, "level set is sealed: a new Version takes a new set");
+    if (ntab == 0) return LSMB_OK;
+    if (!rows || !table_ids || !d_words || !word_off || !num_bits || !num_hashes || !key_off)
+        return fail(LSMB_EINVAL, "null argument");
+    if (ntab >= UINT32_MAX) return fail(LSMB_EINVAL, "more than 2^32-2 tables in one batch");
+    if (reinterpret_cast<uintptr_t>(d_words) & 15) return fail(LSMB_EINVAL, "d_words is not 16-byte aligned");
+    // every table on the host first: nothing is allocated or copied for a batch that fails here
+    uint64_t at = 0;  // the layout's word_off[t]: the slots back to back, the spans' packed source
+    auto off_check = [&](uint64_t t) {
+        if (word_off[t] == at) return LSMB_OK;
+        return fail(LSMB_EINVAL, "word_off[%llu] = %llu, lsmb_build_batch_layout gives %llu", (unsigned long long)t,
+                    (unsigned long long)word_off[t], (unsigned long long)at);
+    };
+    std::vector<uint64_t> nw(ntab);
+    for (uint64_t t = 0; t < ntab; t++) {
+        int rc = off_check(t);
+        if (!rc) rc = lset_add_check(ls, rows[t], table_ids[t]);
+        if (!rc) rc = lset_batch_table_check(ls, ntab, rows[t], num_bits[t], num_hashes[t], keys, key_off + 2 * t);
+        if (rc) {
+            const std::string msg = last_error();
+            return fail(rc, "table %llu of the batch (id %u): %s", (unsigned long long)t, table_ids[t], msg.c_str());
+        }
+        nw[t] = nwords64(num_bits[t]);
+        at += lset_slot_bytes(nw[t]) / 8;
+    }
+    if (int rc = off_check(ntab)) return rc;
+    DevGuard g(ls->c->dev);
+    hipStream_t st = pick_stream(ls->c, stream);
+    std::vector<lsmb_lset::Table> tabs(ntab);
+    for (uint64_t t = 0; t < ntab; t++)
+        lset_batch_table(&tabs[t], table_ids[t], num_bits[t], num_hashes[t], keys, key_off + 2 * t);
+    auto copy = [&]() -> int {
+        if (int rc = lset_stage(ls, nw.data(), ntab)) return rc;
+        for (const LsetSpan& sp : ls->staged.pl.spans)  // one device-to-device copy per chunk touched
+            HIP_TRY(hipMemcpyAsync(lset_at(ls, sp.chunk, sp.off), (const uint8_t*)d_words + sp.src, sp.bytes,
+                                   hipMemcpyDeviceToDevice, st));
+        HIP_TRY(hipStreamSynchronize(st));  // the batch's one wait: the source buffer is free to go
+        return LSMB_OK;
+    };
+    if (int rc = copy()) return lset_abandon(ls, st, rc);  // all or nothing
+    lset_commit(ls, rows, tabs.data(), ntab, 0, 0);  // nothing crossed from the host
+    return LSMB_OK;
+}
+
+int lsmb_lset_stats(const lsmb_lset* ls, uint64_t out[6]) {
+    if (!ls || !out) return fail(LSMB_EINVAL, "null argument");
+    uint64_t ntab = 0, fbytes = 0, cbytes = 0;
+    for (uint32_t r = 0; r < ls->nrows; r++) {
+        ntab += ls->row[r].size();
+        for (const auto& T : ls->row[r]) fbytes += nwords64(T.num_bits) * 8;
+    }
+    for (const auto& ch : ls->chunks) cbytes += ch->buf.bytes;
+    out[0] = ntab;
+    out[1] = ls->inherited;
+    out[2] = ls->up_bytes;
+    out[3] = ls->up_copies;
+    out[4] = cbytes;
+    out[5] = fbytes;
+    return LSMB_OK;
+}
+
+int lsmb_lset_seal(lsmb_lset* ls) {
+    if (!ls) return fail(LSMB_EINVAL, "null level set");
+    if (ls->sealed) return LSMB_OK;
+    // per row: sorted by min_key, ranges disjoint
+    std::vector<uint32_t> order[kLsetMaxRows];
+    uint64_t ntab = 0;
+    for (uint32_t r = 0; r < ls->nrows; r++) {
+        const auto& T = ls->row[r];
+        std::vector<LsetRange> rg(T.size());
+        for (size_t j = 0; j < T.size(); j++)
+            rg[j] = LsetRange{T[j].lo.data(), T[j].lo.size(), T[j].hi.data(), T[j].hi.size(), T[j].id};
+        LsetOrderError err;
+        if (!lset_order_row(rg.data(), (uint32_t)rg.size(), &order[r], &err)) {
+            if (err.inverted) return fail(LSMB_EINVAL, "level set row %u: table %u has min_key > max_key", r, err.id_a);
+            return fail(LSMB_EINVAL, "level set row %u: tables %u and %u overlap (max_key of %u >= min_key of %u)", r,
+                        err.id_a, err.id_b, err.id_a, err.id_b);
+        }
+        ntab += T.size();
+    }
+    // the bound keys' bytes, the descriptors and the search prefixes, each row's
+    // tables in sorted order, rows back to back
+    std::vector<uint8_t> blob;
+    std::vector<LsetTable> d;
+    std::vector<ulonglong2> px;
+    d.reserve(ntab);
+    px.reserve(ntab);
+    for (uint32_t r = 0; r < ls->nrows; r++)
+        for (uint32_t j : order[r]) {
+            const auto& S = ls->row[r][j];
+            LsetTable t;
+            memset(&t, 0, sizeof t);
+            t.words32 = S.words;
+            t.lo = (const uint8_t*)(uintptr_t)blob.size();  // offsets until the blob has its address
+            blob.insert(blob.end(), S.lo.begin(), S.lo.end());
+            t.hi = (const uint8_t*)(uintptr_t)blob.size();
+            blob.insert(blob.end(), S.hi.begin(), S.hi.end());
+            const HostPfx16 pl = host_prefix16(S.lo.data(), S.lo.size()), ph = host_prefix16(S.hi.data(), S.hi.size());
+            t.lo_w0 = pl.w0;
+            t.lo_w1 = pl.w1;
+            t.md = Mod32::make(S.num_bits ? S.num_bits : 1);
+            t.lo_len = (uint32_t)S.lo.size();
+            t.hi_len = (uint32_t)S.hi.size();
+            t.num_bits = S.num_bits;
+            t.k = S.k;
+            t.id = S.id;
+            d.push_back(t);
+            ulonglong2 q;
+            q.x = ph.w0;
+            q.y = ph.w1;
+            px.push_back(q);
+        }
+    DevGuard g(ls->c->dev);
+    HIP_TRY(ls->bounds.ensure(blob.size() + 16));
+    HIP_TRY(ls->desc.ensure(std::max<size_t>(d.size(), 1) * sizeof(LsetTable)));
+    HIP_TRY(ls->pfx.ensure(std::max<size_t>(px.size(), 1) * sizeof(ulonglong2)));
+    const uint8_t* base = (const uint8_t*)ls->bounds.p;
+    for (auto& t : d) {
+        t.lo = base + (uintptr_t)t.lo;
+        t.hi = base + (uintptr_t)t.hi;
+    }
+    if (!blob.empty()) HIP_TRY(hipMemcpyAsync(ls->bounds.p, blob.data(), blob.size(), hipMemcpyHostToDevice, ls->ust));
+    if (!d.empty()) {
+        HIP_TRY(hipMemcpyAsync(ls->desc.p, d.data(), d.size() * sizeof(LsetTable), hipMemcpyHostToDevice, ls->ust));
+        HIP_TRY(hipMemcpyAsync(ls->pfx.p, px.data(), px.size() * sizeof(ulonglong2), hipMemcpyHostToDevice, ls->ust));
+    }
+    HIP_TRY(hipStreamSynchronize(ls->ust));  // blob, d and px are host temporaries
+    memset(&ls->rows, 0, sizeof ls->rows);
+    ls->rows.nrows = ls->nrows;
+    uint64_t at = 0;
+    for (uint32_t r = 0; r < ls->nrows; r++) {
+        const uint32_t m = (uint32_t)ls->row[r].size();
+        if (m) {
+            ls->rows.row[r].hi_pfx = (const ulonglong2*)ls->pfx.p + at;
+            ls->rows.row[r].tab = (const LsetTable*)ls->desc.p + at;
+        }
+        ls->rows.row[r].ntab = m;
+        ls->base[r] = at;
+        at += m;
+    }
+    for (uint32_t r = ls->nrows; r <= kLsetMaxRows; r++) ls->base[r] = at;
+    ls->ids.resize(d.size());
+    for (size_t g = 0; g < d.size(); g++) ls->ids[g] = d[g].id;
+    ls->sealed = true;
+    return LSMB_OK;
+}
+
+int lsmb_lset_rows(const lsmb_lset* ls) { return ls ? (int)ls->nrows : 0; }
+
+uint64_t lsmb_lset_tables(const lsmb_lset* ls, uint32_t row) {
+    return ls && row < kLsetMaxRows ? (uint64_t)ls->row[row].size() : 0;
+}
+
+int lsmb_lset_probe_dev(lsmb_lset* ls, const void* d_data, const void* d_offsets, uint32_t key_len, uint64_t n,
+                        void* d_out, void* stream) {
+    if (int rc = lset_probe_check(ls)) return rc;
+    if (n == 0 || ls->nrows == 0) return LSMB_OK;
+    if (!d_out || !d_data) return fail(LSMB_EINVAL, "null keys or output");
+    DevGuard g(ls->c->dev);
+    KeyBatch kb{(const uint8_t*)d_data, (const uint64_t*)d_offsets, key_len, n};
+    HIP_TRY(launch_lset_probe(kb, ls->rows, (uint32_t*)d_out, ls->c->num_cus, pick_stream(ls->c, stream)));
+    return LSMB_OK;
+}
+
+int lsmb_lset_probe(lsmb_lset* ls, const uint8_t* data, const uint64_t* offsets, uint32_t key_len, uint64_t n,
+                    uint32_t* out) {
+    if (int rc = lset_probe_check(ls)) return rc;
+    if (n == 0 || ls->nrows == 0) return LSMB_OK;
+    if (!out || host_keys_null(data, offsets, key_len, n)) return fail(LSMB_EINVAL, "null keys or output");
+    lsmb_ctx* c = ls->c;
+    DevGuard g(c->dev);
+    const uint64_t obytes = (uint64_t)ls->nrows * n * 4;
+    HIP_TRY(c->out.ensure(obytes));
+    KeyBatch kb;
+    if (int rc = stage_host_keys(c, data, offsets, key_len, n, &kb)) return rc;
+    HIP_TRY(launch_lset_probe(kb, ls->rows, (uint32_t*)c->out.p, c->num_cus, c->st));
+    HIP_TRY(hipMemcpyAsync(out, c->out.p, obytes, hipMemcpyDeviceToHost, c->st));
+    HIP_TRY(hipStreamSynchronize(c->st));
+    return LSMB_OK;
+}
+
+uint64_t lsmb_lset_total_tables(const lsmb_lset* ls) { return ls && ls->sealed ? ls->base[ls->nrows] : 0; }
+
+int lsmb_lset_table_order(const lsmb_lset* ls, uint32_t* ids, uint64_t* row_base) {
+    if (int rc = lset_probe_check(ls)) return rc;
+    if (ids && !ls->ids.empty()) memcpy(ids, ls->ids.data(), ls->ids.size() * sizeof(uint32_t));
+    if (row_base) memcpy(row_base, ls->base, ((size_t)ls->nrows + 1) * sizeof(uint64_t));
+    return LSMB_OK;
+}
+
+uint64_t lsmb_lset_lists_work_bytes(const lsmb_lset* ls, uint64_t n) {
+    if (!ls || !ls->sealed || n > UINT32_MAX) return 0;
+    return lset_lists_plan(n, ls->nrows, ls->base[ls->nrows]).work_bytes;
+}
+
+// The argument checks shared by both lists entry points; G = all tables.
+static int lset_lists_check(const lsmb_lset* ls, uint64_t n, const void* starts, const void* index, uint64_t cap) {
+    if (int rc = lset_probe_check(ls)) return rc;
+    if (n > UINT32_MAX) return fail(LSMB_EINVAL, "more than 2^32-1 keys (the lists hold 32-bit indices)");
+    if (ls->base[ls->nrows] > UINT32_MAX) return fail(LSMB_EINVAL, "more than 2^32-1 tables");
+    if (!starts || (cap && !index)) return fail(LSMB_EINVAL, "null output");
+    return LSMB_OK;
+}
+
+int lsmb_lset_probe_lists_dev(lsmb_lset* ls, const void* d_data, const void* d_offsets, uint32_t key_len, uint64_t n,
+                              void* d_starts, void* d_index, uint64_t cap, void* d_work, uint64_t work_bytes,
+                              void* stream) {
+    if (int rc = lset_lists_check(ls, n, d_starts, d_index, cap)) return rc;
+    const uint64_t G = ls->base[ls->nrows];
+    if (n && G) {
+        if (!d_data) return fail(LSMB_EINVAL, "null keys");
+        if (!d_work || (reinterpret_cast<uintptr_t>(d_work) & 15))
+            return fail(LSMB_EINVAL, "null or misaligned workspace (16-byte alignment)");
+        const uint64_t need = lset_lists_plan(n, ls->nrows, G).work_bytes;
+        if (work_bytes < need)
+            return fail(LSMB_EINVAL, "workspace of %llu bytes, lsmb_lset_lists_work_bytes asks for %llu",
+                        (unsigned long long)work_bytes, (unsigned long long)need);
+    }
+    DevGuard g(ls->c->dev);
+    const hipStream_t st = pick_stream(ls->c, stream);
+    if (n == 0 || G == 0) {
+        HIP_TRY(hipMemsetAsync(d_starts, 0, (G + 1) * 8, st));
+        return LSMB_OK;
+    }
+    KeyBatch kb{(const uint8_t*)d_data, (const uint64_t*)d_offsets, key_len, n};
+    HIP_TRY(launch_lset_lists(kb, ls->rows, G, (uint64_t*)d_starts, (uint32_t*)d_index, cap, d_work, work_bytes,
+                              ls->c->num_cus, st));
+    return LSMB_OK;
+}
+
+int lsmb_lset_probe_lists(lsmb_lset* ls, const uint8_t* data, const uint64_t* offsets, uint32_t key_len, uint64_t n,
+                          uint64_t* starts, uint32_t* index, uint64_t cap) {
+    if (int rc = lset_lists_check(ls, n, starts, index, cap)) return rc;
+    if (n && host_keys_null(data, offsets, key_len, n)) return fail(LSMB_EINVAL, "null keys");
+    const uint64_t G = ls->base[ls->nrows];
+    memset(starts, 0, (G + 1) * 8);
+    if (n == 0 || G == 0) return LSMB_OK;
+    lsmb_ctx* c = ls->c;
+    DevGuard g(c->dev);
+    // the context's output scratch, carved: workspace | starts | index (no
+    // list entry beyond one per row and key)
+    const LsetListsPlan pl = lset_lists_plan(n, ls->nrows, G);
+    const uint64_t dcap = std::min<uint64_t>(cap, pl.pairs);
+    const uint64_t sbytes = ((G + 1) * 8 + kLlAlign - 1) / kLlAlign * kLlAlign;
+    HIP_TRY(c->out.ensure(pl.work_bytes + sbytes + std::max<uint64_t>(dcap, 1) * 4));
+    uint8_t* w = (uint8_t*)c->out.p;
+    uint64_t* d_starts = (uint64_t*)(w + pl.work_bytes);
+    uint32_t* d_index = (uint32_t*)(w + pl.work_bytes + sbytes);
+    KeyBatch kb;
+    if (int rc = stage_host_keys(c, data, offsets, key_len, n, &kb)) return rc;
+    HIP_TRY(launch_lset_lists(kb, ls->rows, G, d_starts, d_index, dcap, w, pl.work_bytes, c->num_cus, c->st));
+    HIP_TRY(hipMemcpyAsync(starts, d_starts, (G + 1) * 8, hipMemcpyDeviceToHost, c->st));
+    HIP_TRY(hipStreamSynchronize(c->st));
+    const uint64_t got = std::min<uint64_t>(starts[G], dcap);
+    if (got) {
+        HIP_TRY(hipMemcpyAsync(index, d_index, got * 4, hipMemcpyDeviceToHost, c->st));
+        HIP_TRY(hipStreamSynchronize(c->st));
+    }
+    return LSMB_OK;
+}
+
+}  // extern "C"

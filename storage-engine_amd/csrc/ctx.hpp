@@ -1,6 +1,8 @@
 // ctx.hpp — the per-GPU context behind lsmb_ctx and the host plumbing shared by
-// capi.hip (the C ABI), build_dev.hip (build orchestration), stream.hip and
-// multi.hip (one process, several GPUs).  Internal.
+// capi.hip and capi_*.hip (the C ABI, one file per handle), build_dev.hip (build
+// orchestration), stream.hip and multi.hip (one process, several GPUs).  Helpers
+// that cross those files are declared here and defined once, in capi.hip.
+// Internal.
 #pragma once
 
 #include <stdint.h>
@@ -78,7 +80,30 @@ void set_last_error(const std::string& s);
         if (e_ != hipSuccess) return ::lsmb::hip_fail(e_, #expr); \
     } while (0)
 
+// A grow-only pinned block (*p, *cap) over a PinnedPool: growth of at least
+// 1.5x, the outgrown block retired to the pool (freed at its owner's teardown),
+// never freed here.  `who` words the LSMB_ENOMEM message.
+inline int pinned_ensure(PinnedPool& pool, uint8_t** p, uint64_t* cap, uint64_t need, const char* who) {
+    if (need <= *cap) return LSMB_OK;
+    const uint64_t want = std::max<uint64_t>(need, *cap + *cap / 2);
+    void* q = nullptr;
+    if (hipHostMalloc(&q, want, hipHostMallocDefault) != hipSuccess) {
+        (void)hipGetLastError();
+        return fail(LSMB_ENOMEM, "%s: %llu bytes of pinned staging", who, (unsigned long long)want);
+    }
+    pool.retire(*p);
+    *p = (uint8_t*)q;
+    *cap = want;
+    return LSMB_OK;
+}
+
 inline uint64_t nwords64(uint32_t num_bits) { return ((uint64_t)num_bits + 63) / 64; }
+
+// The 12-byte header of BloomFilter::serialize (src/bloom/mod.rs:102-115).
+void write_header(uint8_t* out, uint32_t num_bits, uint32_t k);
+
+// offsets[0..n] must be non-decreasing (key i = data[offsets[i] .. offsets[i+1]).
+int check_offsets(const uint64_t* offsets, uint64_t n);
 
 // Reference arguments that would panic (% by zero in get_position, mod.rs:195).
 int check_filter(uint32_t num_bits, uint32_t k);
@@ -149,6 +174,14 @@ namespace lsmb {
 
 // `stream` of an entry point, NULL = the context's own build stream.
 hipStream_t pick_stream(lsmb_ctx* c, void* stream);
+
+// Copies a host key batch into the context's staging buffers (ctx stream).
+int stage_host_keys(lsmb_ctx* c, const uint8_t* data, const uint64_t* offsets, uint32_t key_len, uint64_t n,
+                    KeyBatch* kb);
+// A host key batch of n >= 1 keys that has bytes to read and no pointer to them.
+inline bool host_keys_null(const uint8_t* data, const uint64_t* offsets, uint32_t key_len, uint64_t n) {
+    return !data && (offsets ? offsets[n] > offsets[0] : key_len > 0);
+}
 
 // Device build of one batch on `st` into d_words (OR-accumulate; fresh =
 // BloomFilter::new + inserts: d_words is output-only), chunked so the

@@ -38,7 +38,7 @@ def p(a, t):
 
 
 def slot_words(num_bits):
-    """The arena's slot rule restated (lset_slot_bytes in capi.hip, arena_chunks of
+    """The arena's slot rule restated (lset_slot_bytes in lset_arena.hpp, arena_chunks of
     tests/test_lset_versions.py): max(words * 8, 8) bytes rounded up to 16."""
     nw = (num_bits + 63) // 64
     return (max(nw * 8, 8) + 15) // 16 * 16 // 8

@@ -108,6 +108,24 @@ def test_crc_segment_arithmetic_host(tmp_path):
     assert lsmbloom.crc32_combine(zlib.crc32(a), zlib.crc32(b), len(b)) == zlib.crc32(a + b)
 
 
+def test_arena_placement_host(tmp_path):
+    """lset_place (csrc/lset_arena.hpp), the pure placement every level-set add
+    plans before it allocates or copies, against the one-table-at-a-time bump
+    loop it replaced, restated (tests/cpp/lset_arena_test.cpp): empty batches,
+    16-byte slots, runs ending on the 4 MiB boundary, filters of and past 4 MiB,
+    an inherited tail, a full arena, chains of random batches; slots aligned,
+    disjoint and in bounds, spans tiling the tables, packed offsets equal to the
+    batched build's layout, chunk counts equal to arena_chunks above.  Under
+    ASan and UBSan."""
+    exe = str(tmp_path / "lset_arena_test")
+    src = os.path.join(ROOT, "tests", "cpp", "lset_arena_test.cpp")
+    subprocess.run(["g++", "-std=c++17", "-O1", "-Wall", "-Werror", "-fsanitize=address,undefined",
+                    "-fno-sanitize-recover=undefined", "-o", exe, src], check=True)
+    r = subprocess.run([exe], capture_output=True, text=True, timeout=120)
+    assert r.returncode == 0, r.stdout + r.stderr
+    assert "all passed" in r.stdout
+
+
 def test_version_entry_points_are_exported_and_reject_null():
     L = lsmbloom.lib()
     for name in ("lsmb_lset_derive", "lsmb_lset_add_batch", "lsmb_lset_stats", "lsmb_crc32_seg_dev"):

@@ -20,7 +20,7 @@ LOG=$OUT/sanitize.log
 HIPCC=/opt/rocm/bin/hipcc
 CLANG=/opt/rocm/llvm/bin/clang++
 CLANGC=/opt/rocm/llvm/bin/clang
-SRCS="bloom_build bloom_probe capi multi stream crc32"
+SRCS=$(for f in "$ROOT"/storage-engine_amd/csrc/*.hip; do basename "$f" .hip; done)  # every source of the library
 fails=0
 run() {  # name, command...
   local name=$1; shift
