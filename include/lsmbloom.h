@@ -566,7 +566,9 @@ int lsmb_fset_probe_lists(lsmb_fset* fs, const uint8_t* data, const uint64_t* of
  * a probe writes a caller-chosen table id (the SST id, meta.id) instead of a
  * mask bit per table: a row of thousands of tables costs each key one binary
  * search, one range check and at most one filter walk.  Filters may have any
- * (num_bits, num_hashes), num_hashes = 0 and > 8 included.
+ * (num_bits, num_hashes), num_hashes = 0 and > 8 included.  The Version's L0,
+ * whose tables overlap (src/db/mod.rs:243-252), lives in the same set as its L0
+ * part (LSMB_LSET_ROW_L0, further down), so one sealed set is one Version.
  *   open -> add / add_words / add_batch (any order) -> seal -> probe ... -> close
  *   derive (from a sealed set, sharing its filters) -> add ... -> seal -> probe ... -> close
  * A set belongs to one context.  Adds and seal are used from one thread at a
@@ -581,7 +583,8 @@ void lsmb_lset_close(lsmb_lset* ls);
 
 /* Adds table `table_id` to row `row` from its serialized bloom block, validated
  * exactly as lsmb_fset_add does (LSMB_ECORRUPT) and copied to device memory
- * before the call returns.  LSMB_EINVAL: row >= LSMB_LSET_MAX_LEVELS, table_id
+ * before the call returns.  LSMB_EINVAL: row >= LSMB_LSET_MAX_LEVELS (other than
+ * LSMB_LSET_ROW_L0, below: the set's L0 part), table_id
  * == LSMB_LSET_NONE, num_bits == 0 with num_hashes > 0, an add after seal. */
 int lsmb_lset_add(lsmb_lset* ls, uint32_t row, uint32_t table_id, const uint8_t* block, uint64_t len,
                   const uint8_t* min_key, uint64_t min_len, const uint8_t* max_key, uint64_t max_len);
@@ -658,7 +661,8 @@ int lsmb_lset_stats(const lsmb_lset* ls, uint64_t out[6]);
 
 /* 1 + the highest row added (0 when empty; 0 for NULL). */
 int lsmb_lset_rows(const lsmb_lset* ls);
-/* Tables of one row (0 for NULL or a row >= LSMB_LSET_MAX_LEVELS). */
+/* Tables of one row (0 for NULL or a row >= LSMB_LSET_MAX_LEVELS); row =
+ * LSMB_LSET_ROW_L0: the tables of the L0 part. */
 uint64_t lsmb_lset_tables(const lsmb_lset* ls, uint32_t row);
 
 /* With R = lsmb_lset_rows(ls), out holds R * n values, row-major by level:
@@ -728,6 +732,58 @@ int lsmb_lset_probe_lists_dev(lsmb_lset* ls, const void* d_data, const void* d_o
  * and min(total, cap) entries cross PCIe on the way back. */
 int lsmb_lset_probe_lists(lsmb_lset* ls, const uint8_t* data, const uint64_t* offsets, uint32_t key_len, uint64_t n,
                           uint64_t* starts, uint32_t* index, uint64_t cap);
+
+/* ---- a level set's L0 part: one sealed set answers a Version ---------------- */
+/* DB::get and Snapshot::get walk one Version (src/db/mod.rs:238-267,
+ * src/db/snapshot.rs:40-69): L0 newest first, where the tables' ranges overlap,
+ * then one table per level below.  A level set holds both halves: any add path
+ * called with row = LSMB_LSET_ROW_L0 puts the table into the set's L0 part
+ * instead of a row.  Up to LSMB_LSET_L0_MAX tables, ranges overlapping in any
+ * way; a table's POSITION is its order of arrival (call order, index order
+ * within a batch: a flush is new_levels[0].push(meta), src/db/mod.rs:402).
+ * lsmb_lset_derive keeps the parent's surviving L0 tables in their relative
+ * order, the child's adds follow them (Vec::retain then push,
+ * src/compaction/scheduler.rs:171-174), and drop_ids drops L0 tables exactly as
+ * row tables, the words shared.  So a flush and a compaction are each derive +
+ * add + seal, and the sealed result is the new Version.
+ * The 65th L0 table is LSMB_EINVAL and leaves the set as it was; in a batch
+ * status[t] is LSMB_EINVAL at the first table past the cap (all or nothing) and
+ * lsmb_last_error() names its index and id.  lsmb_lset_seal neither orders nor
+ * checks L0 ranges against each other; an L0 table with min_key > max_key is
+ * LSMB_EINVAL naming its id.
+ * lsmb_lset_rows, _total_tables, _table_order, lsmb_lset_probe* and
+ * lsmb_lset_probe_lists* see the rows only; a set with no L0 table behaves as
+ * before.  lsmb_lset_tables(ls, LSMB_LSET_ROW_L0) is the L0 count, and
+ * lsmb_lset_stats counts L0 tables in [0], [1], [4] and [5] like any other. */
+#define LSMB_LSET_ROW_L0 0x80000000u /* `row` of any add path: the table goes to L0 */
+#define LSMB_LSET_L0_MAX 64
+
+/* T0: the L0 tables (src/db/mod.rs:243-252's version.level(0)).  0 for NULL. */
+uint64_t lsmb_lset_l0_tables(const lsmb_lset* ls);
+
+/* ids[T0] = the table ids in position order (oldest first; src/db/mod.rs:243
+ * reads them in reverse).  Before seal, or NULL: LSMB_EINVAL. */
+int lsmb_lset_l0_order(const lsmb_lset* ls, uint32_t* ids);
+
+/* The whole Version from one hash per key (src/db/mod.rs:238-267,
+ * src/db/snapshot.rs:40-69).  With R = lsmb_lset_rows(ls), T0 = lsmb_lset_l0_tables(ls):
+ *   l0_mask[i] bit j = (min_j <= key i <= max_j) && may_contain(filter j, key i)
+ * for the L0 table at position j (src/sstable/reader.rs:192-199); a reader visits
+ * the set bits from the highest down (version.level(0).iter().rev());
+ *   out[r*n + i] = exactly what lsmb_lset_probe writes.
+ * d_l0_mask (n uint64_t) is always written for n > 0, all zero when T0 == 0;
+ * NULL there is LSMB_EINVAL.  d_out (R * n uint32_t) may be NULL only when
+ * R == 0.  n == 0 writes nothing.  Before seal: LSMB_EINVAL, outputs untouched.
+ * Asynchronous on `stream` (NULL: the context's), no host synchronisation and no
+ * scratch: the sealed set stays read-only, probes on different streams need no
+ * ordering, and the same keys give the same bytes on every run. */
+int lsmb_lset_probe_version_dev(lsmb_lset* ls, const void* d_data, const void* d_offsets, uint32_t key_len,
+                                uint64_t n, void* d_l0_mask, void* d_out, void* stream);
+
+/* Host keys and host outputs; synchronous, through the context's staging as
+ * lsmb_lset_probe (src/db/mod.rs:238-267). */
+int lsmb_lset_probe_version(lsmb_lset* ls, const uint8_t* data, const uint64_t* offsets, uint32_t key_len,
+                            uint64_t n, uint64_t* l0_mask, uint32_t* out);
 
 /* ---- introspection ------------------------------------------------------- */
 

@@ -400,6 +400,46 @@ class LevelSet {
         check(lsmb_lset_probe_dev(ls_, d_data, d_offsets, key_len, n, d_out, stream));
     }
 
+    // The L0 part (every add takes row = LSMB_LSET_ROW_L0): up to
+    // LSMB_LSET_L0_MAX tables with overlapping ranges, position = order of
+    // arrival, survivors of derive first.  With it one sealed set is one
+    // Version (src/db/mod.rs:238-267); a flush or a compaction is derive + add
+    // + seal.
+    uint64_t l0_tables() const { return lsmb_lset_l0_tables(ls_); }
+    std::vector<uint32_t> l0_order() const {
+        std::vector<uint32_t> ids(l0_tables());
+        uint32_t none = 0;
+        check(lsmb_lset_l0_order(ls_, ids.empty() ? &none : ids.data()));
+        return ids;
+    }
+    // mask[i] bit j = min_j <= key i <= max_j && may_contain(filter j, key i)
+    // for the L0 table at position j (read the set bits from the highest
+    // down); ids = probe()'s answer, from the same hash.
+    struct VersionAnswer {
+        std::vector<uint64_t> mask;  // keys.size()
+        std::vector<uint32_t> ids;   // rows() * keys.size()
+    };
+    VersionAnswer probe_version(const std::vector<std::string>& keys) {
+        std::vector<uint64_t> offs(keys.size() + 1, 0);
+        std::string data;
+        for (size_t i = 0; i < keys.size(); i++) {
+            data += keys[i];
+            offs[i + 1] = data.size();
+        }
+        VersionAnswer a;
+        a.mask.assign(keys.size(), 0);
+        a.ids.resize(static_cast<size_t>(rows()) * keys.size());
+        check(lsmb_lset_probe_version(ls_, u8(data), offs.data(), 0, keys.size(), a.mask.data(),
+                                      a.ids.empty() ? nullptr : a.ids.data()));
+        return a;
+    }
+    // Device keys and outputs (d_l0_mask: n uint64_t, d_out: rows() * n
+    // uint32_t, null when the set has no row), asynchronous on `stream`.
+    void probe_version_dev(const void* d_data, const void* d_offsets, uint32_t key_len, uint64_t n, void* d_l0_mask,
+                           void* d_out, void* stream = nullptr) {
+        check(lsmb_lset_probe_version_dev(ls_, d_data, d_offsets, key_len, n, d_l0_mask, d_out, stream));
+    }
+
     // The answer per table (lsmb_lset_probe_lists), keyed by ordinal: table j
     // of row r in the row's sealed order (ascending min_key) is ordinal
     // row_base[r] + j, ids[g] its table id.

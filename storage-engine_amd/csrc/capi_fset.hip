@@ -7,6 +7,7 @@
 #include <vector>
 
 #include "ctx.hpp"
+#include "fset_plan.hpp"
 
 using namespace lsmb;
 
@@ -92,7 +93,8 @@ int fset_probe_event(lsmb_fset* fs, hipStream_t st, hipEvent_t* out) {
 
 // Rebuilds the device descriptors after an add/remove (rare; probes re-use
 // them): the descriptors, and the sorted boundary points of the live tables'
-// key ranges with one in-range mask per region (FsetRanges, kernels.hpp).
+// key ranges with one in-range mask per region (FsetRanges, kernels.hpp), as
+// fset_plan.hpp lays them out.
 int fset_refresh(lsmb_fset* fs) {
     if (!fs->dirty) return LSMB_OK;
     std::vector<const lsmb_fset::Slot*> live;
@@ -102,133 +104,45 @@ int fset_refresh(lsmb_fset* fs) {
             live.push_back(&fs->slot[s]);
             slot_of.push_back(s);
         }
-    // distinct bounds, sorted as Rust's [u8] Ord (std::vector<uint8_t> < is
-    // the same unsigned lexicographic order, a proper prefix first)
-    std::vector<std::vector<uint8_t>> pts;
-    for (const auto* S : live) {
-        pts.push_back(S->lo);
-        pts.push_back(S->hi);
-    }
-    std::sort(pts.begin(), pts.end());
-    pts.erase(std::unique(pts.begin(), pts.end()), pts.end());
-    const uint32_t m = (uint32_t)pts.size();
-    // region masks over descriptor indices: region 2r = (P[r-1], P[r]),
-    // region 2r+1 = {P[r]}
-    std::vector<uint64_t> regmask(2 * m + 1, 0);
-    for (uint32_t d = 0; d < live.size(); d++) {
-        const auto* S = live[d];
-        if (S->hi < S->lo) continue;  // an empty range holds no key
-        const uint32_t a = (uint32_t)(std::lower_bound(pts.begin(), pts.end(), S->lo) - pts.begin());
-        const uint32_t b = (uint32_t)(std::lower_bound(pts.begin(), pts.end(), S->hi) - pts.begin());
-        for (uint32_t reg = 2 * a + 1; reg <= 2 * b + 1; reg++) regmask[reg] |= 1ull << d;
-    }
-    std::vector<uint8_t> blob;
-    std::vector<uint64_t> at;
-    for (const auto& p : pts) {
-        at.push_back(blob.size());
-        blob.insert(blob.end(), p.begin(), p.end());
-    }
+    std::vector<FsetPlanTable> tabs;
+    for (const auto* S : live)
+        tabs.push_back(FsetPlanTable{S->lo.data(), S->lo.size(), S->hi.data(), S->hi.size(), S->num_bits, S->k});
+    FsetPlan pl;  // the points, the region masks and the size classes (fset_plan.hpp)
+    fset_plan(tabs.data(), (uint32_t)tabs.size(), &pl);
+    const uint32_t m = (uint32_t)pl.points.size();
     if (int rc = fset_wait_probes(fs)) return rc;  // no probe may still read the old descriptors
     // grow geometrically from 4 KiB (an outgrown buffer is retired, not freed:
     // DevBuf)
     size_t want = 4096;
-    while (want < blob.size()) want *= 2;
+    while (want < pl.blob.size()) want *= 2;
     HIP_TRY(fs->ranges.ensure(want));
-    if (!blob.empty()) HIP_TRY(hipMemcpyAsync(fs->ranges.p, blob.data(), blob.size(), hipMemcpyHostToDevice, fs->ust));
+    if (!pl.blob.empty())
+        HIP_TRY(hipMemcpyAsync(fs->ranges.p, pl.blob.data(), pl.blob.size(), hipMemcpyHostToDevice, fs->ust));
     const uint8_t* rb = (const uint8_t*)fs->ranges.p;
     std::vector<uint8_t> pbuf(sizeof(FsetPoint) * kFsetMaxPoints + 8 * (2 * kFsetMaxPoints + 1));
     FsetPoint* fp = (FsetPoint*)pbuf.data();
     for (uint32_t j = 0; j < m; j++) {
-        const auto& p = pts[j];
-        uint8_t pad[16] = {0};
-        memcpy(pad, p.data(), std::min<size_t>(16, p.size()));
-        uint64_t w0 = 0, w1 = 0;
-        for (int b = 0; b < 8; b++) {
-            w0 = (w0 << 8) | pad[b];
-            w1 = (w1 << 8) | pad[8 + b];
-        }
-        fp[j].w0 = w0;
-        fp[j].w1 = w1;
-        fp[j].p = rb + at[j];
-        fp[j].len = (uint32_t)p.size();
-        fp[j].pad = 0;
+        fp[j] = pl.points[j];
+        fp[j].p = rb + (uintptr_t)pl.points[j].p;
     }
-    memcpy(pbuf.data() + sizeof(FsetPoint) * m, regmask.data(), 8 * regmask.size());
+    memcpy(pbuf.data() + sizeof(FsetPoint) * m, pl.regmask.data(), 8 * pl.regmask.size());
     HIP_TRY(fs->points.ensure(pbuf.size()));
-    HIP_TRY(hipMemcpyAsync(fs->points.p, pbuf.data(), sizeof(FsetPoint) * m + 8 * regmask.size(), hipMemcpyHostToDevice,
-                           fs->ust));
+    HIP_TRY(hipMemcpyAsync(fs->points.p, pbuf.data(), sizeof(FsetPoint) * m + 8 * pl.regmask.size(),
+                           hipMemcpyHostToDevice, fs->ust));
     fs->rg.pts = (const FsetPoint*)fs->points.p;
     fs->rg.regmask = (const uint64_t*)((const uint8_t*)fs->points.p + sizeof(FsetPoint) * m);
     fs->rg.npts = m;
     std::vector<RangedFilter> d;
-    for (uint32_t j = 0; j < live.size(); j++) {
-        const auto* S = live[j];
-        RangedFilter r;
-        memset(&r, 0, sizeof r);
-        r.f.words32 = (const uint32_t*)S->words.p;
-        r.f.md = Mod32::make(S->num_bits ? S->num_bits : 1);
-        r.f.num_bits = S->num_bits;
-        r.f.k = S->k;
-        r.f.out_bit = slot_of[j];
-        r.f.group = slot_of[j];
-        d.push_back(r);
-    }
+    for (uint32_t j = 0; j < live.size(); j++)
+        d.push_back(fset_plan_desc((const uint32_t*)live[j]->words.p, live[j]->num_bits, live[j]->k, slot_of[j]));
     HIP_TRY(fs->desc.ensure(sizeof(RangedFilter) * 64));
     if (!d.empty())
         HIP_TRY(hipMemcpyAsync(fs->desc.p, d.data(), sizeof(RangedFilter) * d.size(), hipMemcpyHostToDevice, fs->ust));
-    // size classes: descriptors grouped by (num_bits, k); the classes with the
-    // smallest tables go to LDS first (most filters per byte), the rest and
-    // k = 0 filters are walked from L2
-    std::vector<FsetClass> cls;
-    {
-        std::vector<std::pair<uint64_t, uint32_t>> keyd;  // (num_bits << 32 | k, descriptor)
-        for (uint32_t j = 0; j < d.size(); j++)
-            if (d[j].f.k) keyd.push_back({((uint64_t)d[j].f.num_bits << 32) | d[j].f.k, j});
-        std::sort(keyd.begin(), keyd.end());
-        std::vector<FsetClass> all;
-        for (size_t a = 0; a < keyd.size();) {
-            size_t b = a;
-            while (b < keyd.size() && keyd[b].first == keyd[a].first) b++;
-            FsetClass c;
-            memset(&c, 0, sizeof c);
-            c.num_bits = (uint32_t)(keyd[a].first >> 32);
-            c.k = (uint32_t)keyd[a].first;
-            c.md = Mod32::make(c.num_bits);
-            c.md14 = Mod14::make(Mod14::fits(c.num_bits) ? c.num_bits : 1);
-            c.nmem = (uint32_t)(b - a);
-            c.width = c.nmem <= 8 ? 1 : c.nmem <= 16 ? 2 : c.nmem <= 32 ? 4 : 8;
-            for (size_t j = a; j < b; j++) {
-                c.mem[j - a] = (uint8_t)keyd[j].second;
-                c.mask |= 1ull << keyd[j].second;
-            }
-            all.push_back(c);
-            a = b;
-        }
-        auto tbytes = [](const FsetClass& c) { return (((uint64_t)c.num_bits + 31) / 32) * 32 * c.width; };
-        std::stable_sort(all.begin(), all.end(),
-                         [&](const FsetClass& x, const FsetClass& y) { return tbytes(x) < tbytes(y); });
-        uint64_t off = 0, in_lds = 0;
-        for (auto& c : all) {
-            const uint64_t tb = (tbytes(c) + 15) & ~15ull;
-            if (cls.size() < kFsetMaxClasses && off + tb <= kFsetTableBytes) {
-                c.off = (uint32_t)off;
-                off += tb;
-                in_lds |= c.mask;
-                cls.push_back(c);
-            }
-        }
-        uint64_t all_desc = d.size() == 64 ? ~0ull : (1ull << d.size()) - 1;
-        fs->cl.ncls = (uint32_t)cls.size();
-        fs->cl.table_bytes = (uint32_t)off;
-        fs->cl.walk_mask = all_desc & ~in_lds;
-    }
-    for (size_t i = 0; i < cls.size(); i++) fs->cl.cls[i] = cls[i];
-    HIP_TRY(hipStreamSynchronize(fs->ust));  // blob, pbuf and d are host temporaries
+    fs->cl = pl.cl;
+    HIP_TRY(hipStreamSynchronize(fs->ust));  // pl, pbuf and d are host temporaries
     fs->ndesc = (uint32_t)d.size();
-    fs->shared_nb = d.empty() ? 0 : d[0].f.num_bits;
-    fs->shared_k = d.empty() ? 0 : d[0].f.k;
-    for (const auto& r : d)
-        if (r.f.num_bits != fs->shared_nb || r.f.k != fs->shared_k) fs->shared_nb = fs->shared_k = 0;
+    fs->shared_nb = pl.shared_nb;
+    fs->shared_k = pl.shared_k;
     fs->dirty = false;
     return LSMB_OK;
 }

@@ -10,6 +10,7 @@
 
 #include "crc_seg.hpp"
 #include "ctx.hpp"
+#include "fset_plan.hpp"
 #include "lset_arena.hpp"
 #include "lset_lists_plan.hpp"
 #include "lset_order.hpp"
@@ -34,6 +35,15 @@ extern "C" {
 // set bump-allocates only in chunks it allocated itself (own_tail), never in
 // the tail of an inherited one: two children of one parent would collide
 // there, and a sealed set's memory stays read-only for probes in flight.
+//
+// The L0 part (row LSMB_LSET_ROW_L0 of any add): up to LSMB_LSET_L0_MAX tables
+// whose ranges may overlap in any way, kept in order of arrival (a flush is
+// new_levels[0].push(meta), src/db/mod.rs:402; a derived set keeps the
+// parent's survivors in order, then its own adds: Vec::retain then push,
+// src/compaction/scheduler.rs:171-174).  Their words live in the same arena;
+// seal plans them as a filter set plans its slots (fset_plan.hpp), and
+// lsmb_lset_probe_version answers L0 and the rows from one hash per key, so
+// one sealed set is one Version (src/db/mod.rs:238-267).
 namespace lsmb {
 struct LsetChunk {
     int dev = 0;
@@ -63,6 +73,9 @@ struct lsmb_lset {
     };
     std::vector<Table> row[kLsetMaxRows];
     uint32_t nrows = 0;  // 1 + highest row added
+    std::vector<Table> l0;  // position order
+    std::vector<Table>& tables_of(uint32_t r) { return r == LSMB_LSET_ROW_L0 ? l0 : row[r]; }
+    const std::vector<Table>& tables_of(uint32_t r) const { return r == LSMB_LSET_ROW_L0 ? l0 : row[r]; }
     bool sealed = false;
     // filter words: bump-allocated from chunks that are never reallocated;
     // a derived set's inherited chunks come first.  arena is the bump state
@@ -86,6 +99,13 @@ struct lsmb_lset {
     // order) and the first ordinal of every row, base[nrows] = all tables
     std::vector<uint32_t> ids;
     uint64_t base[kLsetMaxRows + 1] = {0};
+    // seal, the L0 part: the boundary points' bytes, FsetPoint[] then the
+    // region masks, RangedFilter[] (descriptor j = position j), and what the
+    // kernels take by value
+    DevBuf l0_bounds, l0_points, l0_desc;
+    FsetRanges l0_rg{};
+    FsetClasses l0_cl{};
+    uint32_t l0_shared_nb = 0, l0_shared_k = 0;
     hipStream_t ust = nullptr;  // uploads
 };
 
@@ -141,8 +161,8 @@ void lset_commit(lsmb_lset* ls, const uint32_t* rows, lsmb_lset::Table* tabs, ui
     for (uint64_t t = 0; t < ntab; t++) {
         tabs[t].chunk = sg.pl.slot[t].chunk;
         tabs[t].words = (const uint32_t*)sg.words[t];
-        ls->row[rows[t]].push_back(std::move(tabs[t]));
-        ls->nrows = std::max(ls->nrows, rows[t] + 1);
+        ls->tables_of(rows[t]).push_back(std::move(tabs[t]));
+        if (rows[t] != LSMB_LSET_ROW_L0) ls->nrows = std::max(ls->nrows, rows[t] + 1);
     }
     ls->up_bytes += up_bytes;
     ls->up_copies += up_copies;
@@ -155,11 +175,23 @@ int lset_range_check(const uint8_t* min_key, uint64_t min_len, const uint8_t* ma
     return LSMB_OK;
 }
 
+// Room for `more` tables in `row`, `l0_before` of them L0 tables that come
+// earlier in the same batch.
+int lset_room_check(const lsmb_lset* ls, uint32_t row, uint64_t more, uint64_t l0_before) {
+    if (row == LSMB_LSET_ROW_L0) {
+        if (ls->l0.size() + l0_before >= LSMB_LSET_L0_MAX)
+            return fail(LSMB_EINVAL, "level set L0 is full (%u tables)", (unsigned)LSMB_LSET_L0_MAX);
+        return LSMB_OK;
+    }
+    if (ls->row[row].size() + more >= UINT32_MAX) return fail(LSMB_EINVAL, "level set row %u is full", row);
+    return LSMB_OK;
+}
+
 int lset_add_common(lsmb_lset* ls, uint32_t row, uint32_t table_id, const uint8_t* words_le, uint32_t num_bits,
                     uint32_t k, const uint8_t* min_key, uint64_t min_len, const uint8_t* max_key, uint64_t max_len) {
     if (int rc = check_filter(num_bits, k)) return rc;
     if (int rc = lset_range_check(min_key, min_len, max_key, max_len)) return rc;
-    if (ls->row[row].size() >= UINT32_MAX) return fail(LSMB_EINVAL, "level set row %u is full", row);
+    if (int rc = lset_room_check(ls, row, 0, 0)) return rc;
     DevGuard g(ls->c->dev);
     const uint64_t nw = nwords64(num_bits);
     lsmb_lset::Table tab;
@@ -184,7 +216,8 @@ int lset_add_common(lsmb_lset* ls, uint32_t row, uint32_t table_id, const uint8_
 int lset_add_check(const lsmb_lset* ls, uint32_t row, uint32_t table_id) {
     if (!ls) return fail(LSMB_EINVAL, "null level set");
     if (ls->sealed) return fail(LSMB_EINVAL, "level set is sealed: a new Version takes a new set");
-    if (row >= kLsetMaxRows) return fail(LSMB_EINVAL, "row %u: a level set has %u rows", row, kLsetMaxRows);
+    if (row >= kLsetMaxRows && row != LSMB_LSET_ROW_L0)
+        return fail(LSMB_EINVAL, "row %u: a level set has %u rows (and LSMB_LSET_ROW_L0)", row, kLsetMaxRows);
     if (table_id == LSMB_LSET_NONE) return fail(LSMB_EINVAL, "table id 0xFFFFFFFF is the probe's 'no table' answer");
     return LSMB_OK;
 }
@@ -223,6 +256,9 @@ void lsmb_lset_close(lsmb_lset* ls) {
         ls->bounds.release();
         ls->desc.release();
         ls->pfx.release();
+        ls->l0_bounds.release();
+        ls->l0_points.release();
+        ls->l0_desc.release();
     }
     delete ls;
 }
@@ -271,6 +307,19 @@ int lsmb_lset_derive(const lsmb_lset* parent, const uint32_t* drop_ids, uint64_t
             ls->row[r].back().chunk = remap[T.chunk];
             ls->inherited++;
         }
+    for (const auto& T : parent->l0) {  // the surviving L0 tables keep their relative order
+        if (std::binary_search(drop.begin(), drop.end(), T.id)) {
+            nd++;
+            continue;
+        }
+        if (remap[T.chunk] == UINT32_MAX) {
+            remap[T.chunk] = (uint32_t)ls->chunks.size();
+            ls->chunks.push_back(parent->chunks[T.chunk]);
+        }
+        ls->l0.push_back(T);
+        ls->l0.back().chunk = remap[T.chunk];
+        ls->inherited++;
+    }
     ls->arena.chunks = ls->chunks.size();  // none of them the child's own: its first add takes a new chunk
     ls->nrows = parent->nrows;
     if (dropped) *dropped = nd;
@@ -291,24 +340,24 @@ void lset_batch_table(lsmb_lset::Table* T, uint32_t id, uint32_t num_bits, uint3
 }
 
 // What both batches check of a table once its filter is known.
-int lset_batch_table_check(const lsmb_lset* ls, uint64_t ntab, uint32_t row, uint32_t num_bits, uint32_t k,
-                           const uint8_t* keys, const uint64_t* koff) {
+int lset_batch_table_check(const lsmb_lset* ls, uint64_t ntab, uint64_t l0_before, uint32_t row, uint32_t num_bits,
+                           uint32_t k, const uint8_t* keys, const uint64_t* koff) {
     if (int rc = check_filter(num_bits, k)) return rc;
     if (koff[1] < koff[0] || koff[2] < koff[1]) return fail(LSMB_EINVAL, "key offsets descend");
     if (int rc = lset_range_check(keys, koff[1] - koff[0], keys, koff[2] - koff[1])) return rc;
-    if (ls->row[row].size() + ntab >= UINT32_MAX) return fail(LSMB_EINVAL, "level set row %u is full", row);
-    return LSMB_OK;
+    return lset_room_check(ls, row, ntab, l0_before);
 }
 
 // One table of lsmb_lset_add_batch: its host-side checks, then *T.
-int lset_batch_check_one(const lsmb_lset* ls, uint64_t ntab, uint32_t row, uint32_t id, const uint8_t* blocks,
+int lset_batch_check_one(const lsmb_lset* ls, uint64_t ntab, uint64_t l0_before, uint32_t row, uint32_t id,
+                         const uint8_t* blocks,
                          const uint64_t* boff, const uint8_t* keys, const uint64_t* koff, lsmb_lset::Table* T) {
     if (int rc = lset_add_check(ls, row, id)) return rc;
     if (boff[1] < boff[0]) return fail(LSMB_EINVAL, "block offsets descend");
     uint32_t k = 0, nb = 0, nw32 = 0;
     if (int rc = lsmb_deserialize_header(blocks ? blocks + boff[0] : nullptr, boff[1] - boff[0], &k, &nb, &nw32))
         return rc;
-    if (int rc = lset_batch_table_check(ls, ntab, row, nb, k, keys, koff)) return rc;
+    if (int rc = lset_batch_table_check(ls, ntab, l0_before, row, nb, k, keys, koff)) return rc;
     lset_batch_table(T, id, nb, k, keys, koff);
     return LSMB_OK;
 }
@@ -388,9 +437,11 @@ int lsmb_lset_add_batch(lsmb_lset* ls, uint64_t ntab, const uint32_t* rows, cons
     int first_rc = LSMB_OK;
     uint64_t first_t = 0;
     std::string first_msg;
+    uint64_t l0_before = 0;  // L0 tables of the batch before table t: the 65th of the set is refused
     for (uint64_t t = 0; t < ntab; t++) {
-        const int rc = lset_batch_check_one(ls, ntab, rows[t], table_ids[t], blocks, block_off + t, keys,
+        const int rc = lset_batch_check_one(ls, ntab, l0_before, rows[t], table_ids[t], blocks, block_off + t, keys,
                                             key_off + 2 * t, &tabs[t]);
+        l0_before += rows[t] == LSMB_LSET_ROW_L0;
         if (status) status[t] = rc;
         if (rc && first_rc == LSMB_OK) {
             first_rc = rc;
@@ -434,10 +485,13 @@ int lsmb_lset_add_batch_dev(lsmb_lset* ls, uint64_t ntab, const uint32_t* rows, 
                     (unsigned long long)word_off[t], (unsigned long long)at);
     };
     std::vector<uint64_t> nw(ntab);
+    uint64_t l0_before = 0;
     for (uint64_t t = 0; t < ntab; t++) {
         int rc = off_check(t);
         if (!rc) rc = lset_add_check(ls, rows[t], table_ids[t]);
-        if (!rc) rc = lset_batch_table_check(ls, ntab, rows[t], num_bits[t], num_hashes[t], keys, key_off + 2 * t);
+        if (!rc)
+            rc = lset_batch_table_check(ls, ntab, l0_before, rows[t], num_bits[t], num_hashes[t], keys, key_off + 2 * t);
+        l0_before += rows[t] == LSMB_LSET_ROW_L0;
         if (rc) {
             const std::string msg = last_error();
             return fail(rc, "table %llu of the batch (id %u): %s", (unsigned long long)t, table_ids[t], msg.c_str());
@@ -471,6 +525,8 @@ int lsmb_lset_stats(const lsmb_lset* ls, uint64_t out[6]) {
         ntab += ls->row[r].size();
         for (const auto& T : ls->row[r]) fbytes += nwords64(T.num_bits) * 8;
     }
+    ntab += ls->l0.size();
+    for (const auto& T : ls->l0) fbytes += nwords64(T.num_bits) * 8;
     for (const auto& ch : ls->chunks) cbytes += ch->buf.bytes;
     out[0] = ntab;
     out[1] = ls->inherited;
@@ -500,6 +556,10 @@ int lsmb_lset_seal(lsmb_lset* ls) {
         }
         ntab += T.size();
     }
+    // L0: any overlap goes, no order to find; a table still has min_key <= max_key
+    for (const auto& T : ls->l0)
+        if (bytes_cmp(T.lo.data(), T.lo.size(), T.hi.data(), T.hi.size()) > 0)
+            return fail(LSMB_EINVAL, "level set L0: table %u has min_key > max_key", T.id);
     // the bound keys' bytes, the descriptors and the search prefixes, each row's
     // tables in sorted order, rows back to back
     std::vector<uint8_t> blob;
@@ -546,7 +606,41 @@ int lsmb_lset_seal(lsmb_lset* ls) {
         HIP_TRY(hipMemcpyAsync(ls->desc.p, d.data(), d.size() * sizeof(LsetTable), hipMemcpyHostToDevice, ls->ust));
         HIP_TRY(hipMemcpyAsync(ls->pfx.p, px.data(), px.size() * sizeof(ulonglong2), hipMemcpyHostToDevice, ls->ust));
     }
-    HIP_TRY(hipStreamSynchronize(ls->ust));  // blob, d and px are host temporaries
+    // the L0 part as a filter set's (fset_plan.hpp): descriptor j = position j = answer bit j
+    FsetPlan pl;
+    std::vector<uint8_t> pbuf;
+    std::vector<RangedFilter> l0d;
+    if (!ls->l0.empty()) {
+        std::vector<FsetPlanTable> pt;
+        for (const auto& T : ls->l0)
+            pt.push_back(FsetPlanTable{T.lo.data(), T.lo.size(), T.hi.data(), T.hi.size(), T.num_bits, T.k});
+        fset_plan(pt.data(), (uint32_t)pt.size(), &pl);
+        const uint32_t m = (uint32_t)pl.points.size();
+        HIP_TRY(ls->l0_bounds.ensure(pl.blob.size() + 16));
+        pbuf.resize(sizeof(FsetPoint) * m + 8 * pl.regmask.size());
+        FsetPoint* fp = (FsetPoint*)pbuf.data();
+        for (uint32_t j = 0; j < m; j++) {
+            fp[j] = pl.points[j];
+            fp[j].p = (const uint8_t*)ls->l0_bounds.p + (uintptr_t)pl.points[j].p;
+        }
+        memcpy(pbuf.data() + sizeof(FsetPoint) * m, pl.regmask.data(), 8 * pl.regmask.size());
+        for (uint32_t j = 0; j < ls->l0.size(); j++)
+            l0d.push_back(fset_plan_desc(ls->l0[j].words, ls->l0[j].num_bits, ls->l0[j].k, j));
+        HIP_TRY(ls->l0_points.ensure(pbuf.size()));
+        HIP_TRY(ls->l0_desc.ensure(l0d.size() * sizeof(RangedFilter)));
+        if (!pl.blob.empty())
+            HIP_TRY(hipMemcpyAsync(ls->l0_bounds.p, pl.blob.data(), pl.blob.size(), hipMemcpyHostToDevice, ls->ust));
+        HIP_TRY(hipMemcpyAsync(ls->l0_points.p, pbuf.data(), pbuf.size(), hipMemcpyHostToDevice, ls->ust));
+        HIP_TRY(hipMemcpyAsync(ls->l0_desc.p, l0d.data(), l0d.size() * sizeof(RangedFilter), hipMemcpyHostToDevice,
+                               ls->ust));
+        ls->l0_rg.pts = (const FsetPoint*)ls->l0_points.p;
+        ls->l0_rg.regmask = (const uint64_t*)((const uint8_t*)ls->l0_points.p + sizeof(FsetPoint) * m);
+        ls->l0_rg.npts = m;
+        ls->l0_cl = pl.cl;
+        ls->l0_shared_nb = pl.shared_nb;
+        ls->l0_shared_k = pl.shared_k;
+    }
+    HIP_TRY(hipStreamSynchronize(ls->ust));  // blob, d, px, pl, pbuf and l0d are host temporaries
     memset(&ls->rows, 0, sizeof ls->rows);
     ls->rows.nrows = ls->nrows;
     uint64_t at = 0;
@@ -570,7 +664,17 @@ int lsmb_lset_seal(lsmb_lset* ls) {
 int lsmb_lset_rows(const lsmb_lset* ls) { return ls ? (int)ls->nrows : 0; }
 
 uint64_t lsmb_lset_tables(const lsmb_lset* ls, uint32_t row) {
+    if (ls && row == LSMB_LSET_ROW_L0) return (uint64_t)ls->l0.size();
     return ls && row < kLsetMaxRows ? (uint64_t)ls->row[row].size() : 0;
+}
+
+uint64_t lsmb_lset_l0_tables(const lsmb_lset* ls) { return ls ? (uint64_t)ls->l0.size() : 0; }
+
+int lsmb_lset_l0_order(const lsmb_lset* ls, uint32_t* ids) {
+    if (int rc = lset_probe_check(ls)) return rc;
+    if (!ids && !ls->l0.empty()) return fail(LSMB_EINVAL, "null ids");
+    for (size_t j = 0; j < ls->l0.size(); j++) ids[j] = ls->l0[j].id;
+    return LSMB_OK;
 }
 
 int lsmb_lset_probe_dev(lsmb_lset* ls, const void* d_data, const void* d_offsets, uint32_t key_len, uint64_t n,
@@ -597,6 +701,53 @@ int lsmb_lset_probe(lsmb_lset* ls, const uint8_t* data, const uint64_t* offsets,
     if (int rc = stage_host_keys(c, data, offsets, key_len, n, &kb)) return rc;
     HIP_TRY(launch_lset_probe(kb, ls->rows, (uint32_t*)c->out.p, c->num_cus, c->st));
     HIP_TRY(hipMemcpyAsync(out, c->out.p, obytes, hipMemcpyDeviceToHost, c->st));
+    HIP_TRY(hipStreamSynchronize(c->st));
+    return LSMB_OK;
+}
+
+// The Version probe of kb on st: d_mask (n u64) and d_out (nrows * n u32,
+// unused when the set has no row).  Without L0 tables the rows' own kernel and
+// a cleared mask; else the fused kernel (lset_version.hip).
+static int lset_version_launch(lsmb_lset* ls, const KeyBatch& kb, uint64_t* d_mask, uint32_t* d_out, hipStream_t st) {
+    if (ls->l0.empty()) {
+        HIP_TRY(hipMemsetAsync(d_mask, 0, kb.n * 8, st));
+        if (ls->nrows) HIP_TRY(launch_lset_probe(kb, ls->rows, d_out, ls->c->num_cus, st));
+        return LSMB_OK;
+    }
+    HIP_TRY(launch_lset_version(kb, ls->rows, (const RangedFilter*)ls->l0_desc.p, (uint32_t)ls->l0.size(), ls->l0_rg,
+                                ls->l0_cl, d_mask, d_out, ls->c->num_cus, st));
+    return LSMB_OK;
+}
+
+int lsmb_lset_probe_version_dev(lsmb_lset* ls, const void* d_data, const void* d_offsets, uint32_t key_len, uint64_t n,
+                                void* d_l0_mask, void* d_out, void* stream) {
+    if (int rc = lset_probe_check(ls)) return rc;
+    if (n == 0) return LSMB_OK;
+    if (!d_l0_mask || !d_data) return fail(LSMB_EINVAL, "null keys or L0 mask");
+    if (!d_out && ls->nrows) return fail(LSMB_EINVAL, "null output for a set with rows");
+    DevGuard g(ls->c->dev);
+    KeyBatch kb{(const uint8_t*)d_data, (const uint64_t*)d_offsets, key_len, n};
+    return lset_version_launch(ls, kb, (uint64_t*)d_l0_mask, (uint32_t*)d_out, pick_stream(ls->c, stream));
+}
+
+int lsmb_lset_probe_version(lsmb_lset* ls, const uint8_t* data, const uint64_t* offsets, uint32_t key_len, uint64_t n,
+                            uint64_t* l0_mask, uint32_t* out) {
+    if (int rc = lset_probe_check(ls)) return rc;
+    if (n == 0) return LSMB_OK;
+    if (!l0_mask || host_keys_null(data, offsets, key_len, n)) return fail(LSMB_EINVAL, "null keys or L0 mask");
+    if (!out && ls->nrows) return fail(LSMB_EINVAL, "null output for a set with rows");
+    lsmb_ctx* c = ls->c;
+    DevGuard g(c->dev);
+    // the context's output scratch: the masks, then the rows' ids
+    const uint64_t mbytes = n * 8, obytes = (uint64_t)ls->nrows * n * 4;
+    HIP_TRY(c->out.ensure(mbytes + obytes));
+    uint64_t* d_mask = (uint64_t*)c->out.p;
+    uint32_t* d_out = (uint32_t*)((uint8_t*)c->out.p + mbytes);
+    KeyBatch kb;
+    if (int rc = stage_host_keys(c, data, offsets, key_len, n, &kb)) return rc;
+    if (int rc = lset_version_launch(ls, kb, d_mask, d_out, c->st)) return rc;
+    HIP_TRY(hipMemcpyAsync(l0_mask, d_mask, mbytes, hipMemcpyDeviceToHost, c->st));
+    if (obytes) HIP_TRY(hipMemcpyAsync(out, d_out, obytes, hipMemcpyDeviceToHost, c->st));
     HIP_TRY(hipStreamSynchronize(c->st));
     return LSMB_OK;
 }

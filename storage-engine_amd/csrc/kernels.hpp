@@ -6,6 +6,7 @@
 #include <stdint.h>
 
 #include "bloom_math.hpp"
+#include "fset_types.hpp"
 
 namespace lsmb {
 
@@ -156,66 +157,6 @@ hipError_t launch_build_batch(const KeyBatch& kb, const BbItem* d_items, uint32_
                               uint32_t ngroup, uint32_t wave_region32, uint32_t group_region32, uint32_t group_lanes,
                               uint64_t* d_words, hipStream_t st, hipEvent_t done = nullptr);
 
-// Filter descriptor for the probe kernels (device-side array).
-struct ProbeFilter {
-    const uint32_t* words32;
-    Mod32 md;
-    uint32_t num_bits;
-    uint32_t k;
-    uint32_t out_bit;  // bit index in the output mask row
-    uint32_t group;    // filters with equal (num_bits, k) share one position walk
-};
-
-// A filter of a filter set (lsmb_fset): the SSTable's filter plus its key
-// range [lo, hi] (SSTable meta min_key/max_key, src/sstable/reader.rs:192).
-struct RangedFilter {
-    ProbeFilter f;  // f.out_bit = the slot
-    const uint8_t* lo;
-    const uint8_t* hi;
-    uint32_t lo_len, hi_len;
-};
-
-// The key ranges of a filter set as sorted boundary points (built on the host
-// per set): the distinct min/max keys of the live tables in Rust [u8] order.
-// For a key, region 2r = strictly between points r-1 and r, region 2r+1 =
-// equal to point r; regmask[region] = the descriptors (bit d = descriptor d)
-// whose [min_key, max_key] holds every key of that region.  So the range
-// pre-check of all F tables is one rank search over <= 2F points.
-constexpr uint32_t kFsetMaxPoints = 128;
-struct FsetPoint {
-    uint64_t w0, w1;   // zero-padded 16-byte prefix as two big-endian words
-    const uint8_t* p;  // the full key (device memory)
-    uint32_t len, pad;
-};
-struct FsetRanges {
-    const FsetPoint* pts;     // npts, sorted
-    const uint64_t* regmask;  // 2 * npts + 1
-    uint32_t npts;
-};
-
-// Size classes of a filter set: the live filters grouped by (num_bits, k),
-// each class a bit-sliced LDS table (entry p = its members' bit p, `width`
-// bytes), the classes together within kFsetTableBytes of LDS.  Filters of
-// classes that do not fit (and k = 0 filters) are walked from L2.
-constexpr uint32_t kFsetMaxClasses = 8;
-constexpr uint32_t kFsetTableBytes = 64 * 1024;
-struct FsetClass {
-    Mod32 md;
-    Mod14 md14;        // valid when num_bits < 2^14 (small): the walk's cheaper reduction
-    uint32_t num_bits, k;
-    uint32_t off;      // byte offset of the class table in the LDS tables
-    uint32_t width;    // entry bytes: 1, 2, 4 or 8 (members <= 8, 16, 32, 64)
-    uint32_t nmem, pad;
-    uint64_t mask;     // the members' descriptor bits
-    uint8_t mem[64];   // member j -> descriptor index
-};
-struct FsetClasses {
-    FsetClass cls[kFsetMaxClasses];  // by value: the kernel reads them as uniform kernel arguments
-    uint32_t ncls;
-    uint32_t table_bytes;  // LDS bytes of all class tables
-    uint64_t walk_mask;    // descriptors walked from L2
-};
-
 // out[i] bit s = (lo_s <= key i <= hi_s) && may_contain(filter s, key i), for
 // the nfilt (<= 64) descriptors at d_filters (device memory).  One class
 // holding every descriptor takes the bit-sliced kernel with a compile-time
@@ -275,6 +216,16 @@ hipError_t launch_lset_probe(const KeyBatch& kb, const LsetRows& rows, uint32_t*
 // stride >= kb.n.  Ids are the caller's and need not be unique; ordinals are.
 hipError_t launch_lset_probe_ordinals(const KeyBatch& kb, const LsetRows& rows, uint32_t* d_out, uint64_t stride,
                                       int num_cus, hipStream_t st);
+
+// A whole Version from one hash per key (lset_version.hip): the rows as
+// launch_lset_probe answers them (d_out, may be null when rows.nrows == 0),
+// and d_l0_mask[i] bit j = (lo_j <= key i <= hi_j) && may_contain(filter j,
+// key i) for the set's nl0 (1 .. 64) L0 tables, descriptor j = the table at
+// position j with out_bit j (d_l0, rg and cl as fset_plan.hpp plans them,
+// cl.table_bytes <= kFsetTableBytes).  Read-only, no scratch.
+hipError_t launch_lset_version(const KeyBatch& kb, const LsetRows& rows, const RangedFilter* d_l0, uint32_t nl0,
+                               const FsetRanges& rg, const FsetClasses& cl, uint64_t* d_l0_mask, uint32_t* d_out,
+                               int num_cus, hipStream_t st);
 
 // The level set's answer per table (lset_lists.hip): with G = the tables of
 // all rows, for every ordinal g < G, d_index[d_starts[g] .. d_starts[g+1]) =

@@ -1,0 +1,101 @@
+// lset_version.hip — the fused Version probe of a level set for gfx950
+// (MI355X): the batched form of DB::get's whole walk (src/db/mod.rs:238-267,
+// Snapshot::get src/db/snapshot.rs:40-69) — L0 newest first, where tables
+// overlap, then one table per level below — from ONE hash per key.
+//
+// Per workgroup, once: the L0 descriptors, the boundary points and region
+// masks of the L0 ranges, and the bit-sliced class tables of the L0 filters
+// into LDS, exactly as k_fset_classes stages them (fset_dev.hpp).
+// Per key (one lane per key, grid-stride): the hash and the 16-byte prefix
+// once; then
+//   L0    one region lookup for the in-range mask, one walk and k LDS reads
+//         per class with an in-range member, an L2 walk with early exit for
+//         the filters outside the classes (classes_answer): bit j of the mask
+//         = (min_j <= key <= max_j) && may_contain(filter j, key) for the L0
+//         table at position j, so a reader visits set bits from the highest
+//         down (version.level(0).iter().rev());
+//   rows  the walk of lset.hip (lset_rows_walk), ids stored as k_lset_probe
+//         stores them.
+// csrc/fset_plan.hpp states the L0 answer in plain C++ (fset_plan_answer),
+// csrc/lset_order.hpp the rows' search (lset_find).
+#include <type_traits>
+
+#include "fset_dev.hpp"
+#include "kernels.hpp"
+#include "keyorder.hpp"
+#include "keysrc.hpp"
+#include "lset_walk.hpp"
+
+namespace lsmb {
+namespace {
+
+using ks::Fixed16;
+using ks::FixedN;
+using ks::VarLen;
+
+// k_fset_classes' geometry (fset_dev.hpp): 1024-thread workgroups, two per CU
+// for 16-B keys, one for the other key sources, so a CU builds the class
+// tables at most twice.  The row search adds no register beyond that cap's 64
+// (16-B keys) and 128: no scratch in any instantiation (DESIGN.md section 4.4
+// records the compiled figures).
+template <class Src>
+__global__ __launch_bounds__(kClassBlock, 4 * class_wgs_per_cu<Src>()) void k_lset_version(
+    Src src, uint64_t n, LsetRows rows, const RangedFilter* __restrict__ l0, uint32_t nl0, FsetRanges rg,
+    FsetClasses cl, uint64_t* __restrict__ mask, uint32_t* __restrict__ out) {
+    extern __shared__ __align__(16) uint8_t smem_raw[];
+    __shared__ FsetClassLds S;
+    __shared__ FsetLds L;
+    stage_classes(l0, nl0, cl, S);
+    stage_ranges(rg, L);
+    __syncthreads();
+    build_class_tables(cl, S, smem_raw);
+    __syncthreads();
+    const MaskOut mo{reinterpret_cast<uint8_t*>(mask), 8};
+    const uint32_t npts = rg.npts;
+    const uint64_t gs = (uint64_t)gridDim.x * blockDim.x;
+    for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gs) {
+        const H128 h = src.hash(i);
+        const uint8_t* kp = src.bytes(i);
+        const uint64_t kl = src.key_len(i);
+        const Pfx16 kx = prefix16(kp, kl);
+        const uint64_t rm = L.regmask[key_region(kx, kp, kl, L, npts)];
+        // descriptor d is the L0 table at position d: the descriptor bits are the answer
+        mo.put(i, classes_answer(h, rm, cl, S, smem_raw));
+        lset_rows_walk<false>(h, kx, kp, kl, rows, out, n, i);
+    }
+}
+
+template <class Src>
+hipError_t lset_version_with(const Src& src, uint64_t n, const LsetRows& rows, const RangedFilter* d_l0, uint32_t nl0,
+                             const FsetRanges& rg, const FsetClasses& cl, uint64_t* d_mask, uint32_t* d_out,
+                             int num_cus, hipStream_t st) {
+    uint64_t g = (n + kClassBlock - 1) / kClassBlock;
+    const uint64_t gmax = (uint64_t)num_cus * class_wgs_per_cu<Src>();
+    if (g > gmax) g = gmax;
+    const size_t smem = cl.table_bytes;
+    hipFuncSetAttribute((const void*)k_lset_version<Src>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
+    k_lset_version<Src><<<dim3((uint32_t)g), dim3(kClassBlock), smem, st>>>(src, n, rows, d_l0, nl0, rg, cl, d_mask,
+                                                                              d_out);
+    return hipGetLastError();
+}
+
+}  // namespace
+
+hipError_t launch_lset_version(const KeyBatch& kb, const LsetRows& rows, const RangedFilter* d_l0, uint32_t nl0,
+                               const FsetRanges& rg, const FsetClasses& cl, uint64_t* d_l0_mask, uint32_t* d_out,
+                               int num_cus, hipStream_t st) {
+    if (kb.n == 0) return hipSuccess;
+    if (rows.nrows > kLsetMaxRows || nl0 == 0 || nl0 > 64 || rg.npts > kFsetMaxPoints || cl.ncls > kFsetMaxClasses ||
+        cl.table_bytes > kFsetTableBytes)
+        return hipErrorInvalidValue;
+    if (!d_l0_mask || (rows.nrows && !d_out)) return hipErrorInvalidValue;
+    if (kb.offsets)
+        return lset_version_with(VarLen{kb.data, kb.offsets}, kb.n, rows, d_l0, nl0, rg, cl, d_l0_mask, d_out, num_cus,
+                                 st);
+    if (kb.key_len == 16 && (reinterpret_cast<uintptr_t>(kb.data) & 15) == 0)
+        return lset_version_with(Fixed16{reinterpret_cast<const uint4*>(kb.data)}, kb.n, rows, d_l0, nl0, rg, cl,
+                                 d_l0_mask, d_out, num_cus, st);
+    return lset_version_with(FixedN{kb.data, kb.key_len}, kb.n, rows, d_l0, nl0, rg, cl, d_l0_mask, d_out, num_cus, st);
+}
+
+}  // namespace lsmb

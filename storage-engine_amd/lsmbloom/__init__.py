@@ -32,6 +32,8 @@ LSMB_ECORRUPT = -4
 LSMB_ENOMEM = -5
 LSMB_LSET_MAX_LEVELS = 8
 LSMB_LSET_NONE = 0xFFFFFFFF  # LevelSet.probe: no table of this row
+LSMB_LSET_ROW_L0 = 0x80000000  # `row` of any LevelSet add: the table goes to the set's L0 part
+LSMB_LSET_L0_MAX = 64
 
 u8p = ctypes.POINTER(ctypes.c_uint8)
 u32p = ctypes.POINTER(ctypes.c_uint32)
@@ -120,6 +122,10 @@ SIGNATURES = {
                                                  vp, ctypes.c_uint64, vp]),
     "lsmb_lset_probe_lists": (ctypes.c_int, [vp, u8p, u64p, ctypes.c_uint32, ctypes.c_uint64, u64p, u32p,
                                              ctypes.c_uint64]),
+    "lsmb_lset_l0_tables": (ctypes.c_uint64, [vp]),
+    "lsmb_lset_l0_order": (ctypes.c_int, [vp, u32p]),
+    "lsmb_lset_probe_version_dev": (ctypes.c_int, [vp, vp, vp, ctypes.c_uint32, ctypes.c_uint64, vp, vp, vp]),
+    "lsmb_lset_probe_version": (ctypes.c_int, [vp, u8p, u64p, ctypes.c_uint32, ctypes.c_uint64, u64p, u32p]),
     "lsmb_build_strategy": (ctypes.c_char_p, [ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint64]),
     "lsmb_host_max_keys": (ctypes.c_uint64, []),
     "lsmb_build_sweeps": (ctypes.c_int, [ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint64]),
@@ -757,6 +763,11 @@ class LevelSet:
 
     probe(keys)[r, i] = table_id of the one table t of row r with
     min_t <= key_i <= max_t and may_contain(filter t, key_i), else LSMB_LSET_NONE.
+
+    Every add also takes row=LSMB_LSET_ROW_L0: the table goes to the set's L0
+    part (up to LSMB_LSET_L0_MAX tables, overlapping ranges, position = order
+    of arrival), and probe_version answers L0 and the rows together, so one
+    sealed set is one Version; a flush or a compaction is derive + add + seal.
     """
 
     def __init__(self, ctx=None):
@@ -919,6 +930,56 @@ class LevelSet:
         offs = vp(offsets.data_ptr()) if offsets is not None else None
         _check(lib().lsmb_lset_probe_dev(self.h, vp(data.data_ptr()), offs, key_len, n, vp(out.data_ptr()),
                                          Context._stream(stream)))
+
+    def l0_tables(self):
+        """Tables of the L0 part (lsmb_lset_l0_tables)."""
+        return int(lib().lsmb_lset_l0_tables(self.h))
+
+    def l0_order(self):
+        """-> uint32[l0_tables()]: the L0 tables' ids in position order,
+        oldest first (bit j of probe_version's mask is position j)."""
+        ids = np.zeros(max(self.l0_tables(), 1), dtype=np.uint32)
+        _check(lib().lsmb_lset_l0_order(self.h, _p(ids, u32p)))
+        return ids[:self.l0_tables()]
+
+    def probe_version(self, data, offsets=None, key_len=0):
+        """Packed host keys (as probe) -> (mask uint64[n], ids uint32[rows(), n])
+        from one hash per key (lsmb_lset_probe_version): mask[i] bit j =
+        min_j <= key_i <= max_j and may_contain(filter j, key_i) for the L0
+        table at position j (a reader visits set bits from the highest down),
+        ids exactly probe()'s."""
+        data = np.ascontiguousarray(data, dtype=np.uint8).reshape(-1)
+        if offsets is not None:
+            offsets = np.ascontiguousarray(offsets, dtype=np.uint64)
+            n = offsets.size - 1
+            op = _p(offsets, u64p)
+        else:
+            n = data.size // key_len if key_len else 0
+            op = None
+        mask = np.zeros(n, dtype=np.uint64)
+        out = np.empty((self.rows(), n), dtype=np.uint32)
+        if data.size == 0:
+            data = np.zeros(1, np.uint8)
+        _check(lib().lsmb_lset_probe_version(self.h, _p(data, u8p), op, key_len, n,
+                                             _p(mask if n else np.zeros(1, np.uint64), u64p),
+                                             _p(out, u32p) if out.size else None))
+        return mask, out
+
+    def probe_version_keys(self, keys):
+        """list of bytes -> (mask, ids) as probe_version."""
+        lens = np.array([len(k) for k in keys], dtype=np.uint64)
+        offs = np.zeros(len(keys) + 1, dtype=np.uint64)
+        np.cumsum(lens, out=offs[1:])
+        return self.probe_version(np.frombuffer(b"".join(bytes(k) for k in keys), dtype=np.uint8), offs)
+
+    def probe_version_dev(self, data, n, mask, out, offsets=None, key_len=0, stream=None):
+        """Device keys -> device answers (lsmb_lset_probe_version_dev): mask an
+        int64 / uint64 tensor of n, out an int32 / uint32 tensor of rows() * n
+        as probe_dev's (None when the set has no row)."""
+        offs = vp(offsets.data_ptr()) if offsets is not None else None
+        _check(lib().lsmb_lset_probe_version_dev(self.h, vp(data.data_ptr()), offs, key_len, n, vp(mask.data_ptr()),
+                                                 vp(out.data_ptr()) if out is not None else None,
+                                                 Context._stream(stream)))
 
     def total_tables(self):
         """Tables of all rows (0 before seal): the lists' ordinals are 0 .. total_tables() - 1."""
