@@ -570,8 +570,19 @@ static int probe_common(lsmb_ctx* c, const uint32_t* const* wptrs, const uint32_
         return LSMB_OK;
     }
     // Descriptors go to the device only when they change (a probe loop over the
-    // same level filters re-uses them); the upload waits for the last kernel
-    // that read the previous set, so no host sync sits between repeat probes.
+    // same level filters re-uses them).  filt_desc is shared by every generic
+    // probe on this context, whatever its stream, so the generic probes are
+    // kept in one chain: desc_done is completed by the last one's kernel
+    // (launch_done), and the next one starts after it.
+    //  - New descriptors: the host waits for desc_done before it refills the
+    //    pinned staging and queues the upload.  The chain makes that enough:
+    //    once the last kernel is done, so is every earlier one, on any stream.
+    //  - Same descriptors on another stream than the last probe's: that stream
+    //    waits for desc_done, or its kernel could run before the upload still
+    //    queued on the other stream and read what filt_desc held before.
+    //  - Same descriptors on the same stream: stream order already holds, so
+    //    no wait packet and no host sync sits between repeat probes; they stay
+    //    back-to-back kernels.
     HIP_TRY(c->filt_desc.ensure(sizeof(ProbeFilter) * 64));
     const bool same = c->desc_uploaded.size() == nfilt &&
                       memcmp(c->desc_uploaded.data(), c->hfilt.data(), sizeof(ProbeFilter) * nfilt) == 0;
@@ -582,9 +593,16 @@ static int probe_common(lsmb_ctx* c, const uint32_t* const* wptrs, const uint32_
         HIP_TRY(hipMemcpyAsync(c->filt_desc.p, c->desc_pinned, sizeof(ProbeFilter) * nfilt,
                                hipMemcpyHostToDevice, st));
         c->desc_uploaded = c->hfilt;
+    } else if (c->desc_stream != st) {
+        HIP_TRY(hipStreamWaitEvent(st, c->desc_done, 0));
     }
-    HIP_TRY(launch_probe(kb, c->hfilt.data(), nfilt, (ProbeFilter*)c->filt_desc.p, d_out, c->num_cus, st,
-                         c->desc_done));  // (the dispatch completes the guard event)
+    c->desc_stream = st;
+    const hipError_t e = launch_probe(kb, c->hfilt.data(), nfilt, (ProbeFilter*)c->filt_desc.p, d_out, c->num_cus, st,
+                                      c->desc_done);  // (the dispatch completes the guard event)
+    if (e != hipSuccess) {
+        (void)hipEventRecord(c->desc_done, st);  // (a failed launch may not have completed it; an upload may be queued)
+        return hip_fail(e, "launch_probe");
+    }
     return LSMB_OK;
 }
 

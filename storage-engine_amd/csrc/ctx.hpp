@@ -117,6 +117,29 @@ constexpr uint64_t kDefaultHostMaxKeys = 2048;  // SST-size
 
 }  // namespace lsmb
 
+// Calls on different streams.  Every device entry point takes the caller's
+// stream, and three groups of device buffers below are shared by all calls on
+// the context.  Each group has one event that the last user's final kernel
+// completes itself (launch_done: no marker packet), and the stream of that
+// user; a call on the same stream relies on stream order alone:
+//  - build workspace (ws_*): ws_done / ws_stream.  A tiled or partition build
+//    on another stream than the last one's waits for ws_done on its stream
+//    before anything of it runs (build_dev, build_dev.hip).  Builds are
+//    thereby serialised in call order; Lds and Atomic builds take no
+//    workspace and are not ordered.
+//  - probe descriptors (filt_desc, desc_pinned): desc_done / desc_stream.  A
+//    generic probe with new descriptors waits for desc_done on the host
+//    before it refills the staging and uploads; one with the uploaded
+//    descriptors on another stream waits for it on that stream
+//    (probe_common, capi.hip).  Generic probes are thereby one chain in call
+//    order; bit-sliced probes read no descriptors and are not ordered.
+//  - batched-build items (bb_items[s], bb_pin[s]): bb_done[s] / bb_stream[s],
+//    per slot, slots alternating by call.  The host waits for bb_done[s]
+//    before it refills slot s (two batches later), and a batch on another
+//    stream than the slot's last waits for it on its stream before the copy
+//    (bb_enqueue, capi_build_batch.hip).
+// The host-side state itself is not locked: calls on one context come from
+// one thread at a time.
 struct lsmb_ctx {
     int dev = 0;
     int num_cus = 256;
@@ -140,6 +163,7 @@ struct lsmb_ctx {
     std::vector<lsmb::ProbeFilter> desc_uploaded;  // what filt_desc currently holds
     lsmb::ProbeFilter* desc_pinned = nullptr;      // pinned staging for descriptor uploads
     hipEvent_t desc_done = nullptr;                // last kernel that read filt_desc
+    hipStream_t desc_stream = nullptr;             // stream of the last generic probe (nullptr: none yet)
     std::vector<uint64_t> offs_tmp;
     bool timing = true;                  // per-build HIP events (lsmb_set_timing)
     // host-memory builds: two staging slots, H2D on `cst` overlapping the
