@@ -319,6 +319,15 @@ int lsmb_crc32_dev(lsmb_ctx* ctx, uint32_t crc, const void* d_data, uint64_t len
  * Asynchronous on `stream`, no host synchronisation inside.  This is what
  * lsmb_lset_add_batch checks its CRCs with. */
 int lsmb_crc32_seg_dev(lsmb_ctx* ctx, const void* d_segs, uint64_t nseg, void* d_out, void* stream);
+/* Many small device-to-device copies in one launch (the surviving SSTable filters a Version
+ * edit moves out of sparse arena chunks, src/compaction/scheduler.rs:163-177, src/db/mod.rs:402):
+ * d_segs is nseg triples {const void* src; void* dst; uint64_t len} in device memory, src and
+ * dst 16-byte aligned, len a multiple of 16 (0: nothing moves).  One wave per segment; cut a
+ * long copy into several segments to spread it.  Segments whose ranges overlap, within one
+ * segment or across segments, are undefined.  Asynchronous on `stream` (NULL: the context's), no
+ * host synchronisation inside; nseg == 0 is LSMB_OK.  LSMB_EINVAL: NULL ctx, NULL d_segs with
+ * nseg > 0.  This is what lsmb_lset_derive_packed moves its tables with. */
+int lsmb_copy_segs_dev(lsmb_ctx* ctx, const void* d_segs, uint64_t nseg, void* stream);
 int lsmb_build_block_crc(lsmb_ctx* ctx, const uint8_t* data, const uint64_t* offsets, uint32_t key_len, uint64_t n,
                          uint32_t num_bits, uint32_t num_hashes, uint8_t* block, uint64_t block_len, uint32_t* crc);
 
@@ -570,7 +579,7 @@ int lsmb_fset_probe_lists(lsmb_fset* fs, const uint8_t* data, const uint64_t* of
  * whose tables overlap (src/db/mod.rs:243-252), lives in the same set as its L0
  * part (LSMB_LSET_ROW_L0, further down), so one sealed set is one Version.
  *   open -> add / add_words / add_batch (any order) -> seal -> probe ... -> close
- *   derive (from a sealed set, sharing its filters) -> add ... -> seal -> probe ... -> close
+ *   derive / derive_packed (from a sealed set, sharing its filters) -> add ... -> seal -> probe ... -> close
  * A set belongs to one context.  Adds and seal are used from one thread at a
  * time; a sealed set is only read, so probes on different streams need no
  * ordering among themselves.  Close a set once its probes have completed. */
@@ -616,6 +625,33 @@ int lsmb_lset_seal(lsmb_lset* ls);
 int lsmb_lset_derive(const lsmb_lset* parent, const uint32_t* drop_ids, uint64_t ndrop,
                      uint64_t* dropped, lsmb_lset** out);
 
+/* lsmb_lset_derive that also REPACKS sparse arena chunks on the device, for a store that edits
+ * its Version for days (a compaction, src/compaction/scheduler.rs:163-177, or a flush,
+ * src/db/mod.rs:402, is derive + add + seal, and every plain derive leaves the child's add a
+ * fresh chunk for one small filter while each old chunk lives as long as one table in it).
+ * With live(c) = the slot bytes (filter words rounded up to 16) of the surviving tables in the
+ * parent's chunk c, chunk c is EVACUATED iff live(c) > 0 and live(c) * 1e6 < min_ppm * bytes(c);
+ * under min_ppm = LSMB_LSET_REPACK_ALL iff live(c) > 0.  All survivors of an evacuated chunk are
+ * copied, device to device, into chunks the child allocates itself, and the child holds no
+ * reference to the evacuated chunk; all other survivors stay shared as lsmb_lset_derive leaves
+ * them.  A filter in a chunk of its own has live == bytes, so only LSMB_LSET_REPACK_ALL moves it;
+ * min_ppm == 0 moves nothing and is lsmb_lset_derive exactly.  Tables, rows, L0 positions, ids
+ * and ranges of the child are those of lsmb_lset_derive in every case.
+ * The child's next add continues in the chunk the moved tables went to instead of taking a new
+ * one.  moved (may be NULL): [0] tables moved, [1] their slot bytes.
+ * The copy is one kernel launch (lsmb_copy_segs_dev's) on `stream` (NULL: a stream of the
+ * child's own) followed by ONE synchronisation of it; on return the parent may be closed and the
+ * child is ready for adds and lsmb_lset_seal.  The parent's memory is only read: its probes on
+ * other streams or threads need no ordering with this call.  ALL OR NOTHING: on any failure
+ * *out == NULL, the chunks the call allocated are released and the parent is as it was.
+ * LSMB_EINVAL as lsmb_lset_derive, and for min_ppm > LSMB_LSET_REPACK_ALL.
+ * In lsmb_lset_stats moved tables count in [0], [1], [4] and [5] and add nothing to [2] and [3]:
+ * no byte crosses PCIe. */
+#define LSMB_LSET_REPACK_ALL 1000001u
+int lsmb_lset_derive_packed(const lsmb_lset* parent, const uint32_t* drop_ids, uint64_t ndrop,
+                            uint32_t min_ppm, uint64_t* dropped, uint64_t moved[2], lsmb_lset** out,
+                            void* stream);
+
 /* ntab tables in one call (a store opening its SSTables, SSTable::open -> deserialize,
  * src/sstable/reader.rs:78-82): table t goes to rows[t] with id table_ids[t]; its serialized block is
  * blocks[block_off[t] .. block_off[t+1]), its min_key keys[key_off[2t] .. key_off[2t+1]), its
@@ -655,8 +691,8 @@ int lsmb_lset_add_batch_dev(lsmb_lset* ls, uint64_t ntab, const uint32_t* rows, 
  * out[0] tables; [1] tables inherited by lsmb_lset_derive; [2] filter bytes this set uploaded;
  * [3] host-to-device copy calls this set issued for filter words; [4] device bytes of all arena
  * chunks this set keeps alive (its own and shared ones); [5] filter bytes of its tables.
- * [5]/[4] is the occupancy.  A caller rebuilds a fresh set when a long chain of edits has left
- * it low.  LSMB_EINVAL: NULL set or out. */
+ * [5]/[4] is the occupancy.  A chain of plain derives leaves it low; lsmb_lset_derive_packed
+ * keeps it up on the device, without a rebuild from the host.  LSMB_EINVAL: NULL set or out. */
 int lsmb_lset_stats(const lsmb_lset* ls, uint64_t out[6]);
 
 /* 1 + the highest row added (0 when empty; 0 for NULL). */

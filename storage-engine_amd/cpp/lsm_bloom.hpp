@@ -320,6 +320,20 @@ class LevelSet {
         check(lsmb_lset_derive(ls_, drop_ids.data(), drop_ids.size(), dropped, &h));
         return std::unique_ptr<LevelSet>(new LevelSet(h));
     }
+    // derive that also repacks sparse arena chunks on the device
+    // (lsmb_lset_derive_packed; src/compaction/scheduler.rs:163-177,
+    // src/db/mod.rs:402): the survivors of every chunk of this set whose live
+    // share is below min_ppm millionths (LSMB_LSET_REPACK_ALL: every survivor)
+    // move into a chunk of the new set's own, device to device on stream, and
+    // the new set's next add continues there.  moved: {tables, slot bytes}.
+    std::unique_ptr<LevelSet> derive_packed(const std::vector<uint32_t>& drop_ids, uint32_t min_ppm,
+                                            uint64_t* dropped = nullptr, std::array<uint64_t, 2>* moved = nullptr,
+                                            void* stream = nullptr) const {
+        lsmb_lset* h = nullptr;
+        check(lsmb_lset_derive_packed(ls_, drop_ids.data(), drop_ids.size(), min_ppm, dropped,
+                                      moved ? moved->data() : nullptr, &h, stream));
+        return std::unique_ptr<LevelSet>(new LevelSet(h));
+    }
     // Many tables in one call (lsmb_lset_add_batch): all or nothing; crcs
     // (optional) are checked on the device copies.  Throws as add does for the
     // first failing table; status (optional) receives every table's own code.

@@ -1,11 +1,13 @@
 // capi_lset.hip — the C ABI of the level set (lsmb_lset_*, include/lsmbloom.h).
 // Host-side plumbing only; the placement of filters in the arena is planned in
-// lset_arena.hpp, the kernels are in lset.hip, lset_lists.hip and crc32.hip.
+// lset_arena.hpp, a repacking derive in lset_repack.hpp; the kernels are in
+// lset.hip, lset_lists.hip, lset_repack.hip and crc32.hip.
 #include <string.h>
 
 #include <algorithm>
 #include <memory>
 #include <string>
+#include <utility>
 #include <vector>
 
 #include "crc_seg.hpp"
@@ -14,6 +16,7 @@
 #include "lset_arena.hpp"
 #include "lset_lists_plan.hpp"
 #include "lset_order.hpp"
+#include "lset_repack.hpp"
 
 using namespace lsmb;
 
@@ -35,6 +38,10 @@ extern "C" {
 // set bump-allocates only in chunks it allocated itself (own_tail), never in
 // the tail of an inherited one: two children of one parent would collide
 // there, and a sealed set's memory stays read-only for probes in flight.
+// Left alone, a chain of edits therefore holds a chunk per edit for one small
+// filter each; lsmb_lset_derive_packed moves the survivors of sparse chunks
+// into a chunk of the child's own (k_copy_segs, device to device) and leaves
+// the bump pointer there for the edit's add.
 //
 // The L0 part (row LSMB_LSET_ROW_L0 of any add): up to LSMB_LSET_L0_MAX tables
 // whose ranges may overlap in any way, kept in order of arrival (a flush is
@@ -280,51 +287,138 @@ int lsmb_lset_add_words(lsmb_lset* ls, uint32_t row, uint32_t table_id, const ui
                            max_len);
 }
 
-int lsmb_lset_derive(const lsmb_lset* parent, const uint32_t* drop_ids, uint64_t ndrop, uint64_t* dropped,
-                     lsmb_lset** out) {
+namespace {
+
+// The survivors the plan (lset_repack.hpp) moved, already in the child's rows
+// with the parent's addresses: their slots in chunks of the child's own, one
+// k_copy_segs launch on st (NULL: the child's upload stream) and its wait, then
+// the commit.  The items cross through the child's pinned staging.
+int lset_repack_moved(lsmb_lset* ls, const std::vector<lsmb_lset::Table*>& mv, void* stream, uint64_t* moved_bytes) {
+    DevGuard g(ls->c->dev);
+    const hipStream_t st = stream ? (hipStream_t)stream : ls->ust;
+    std::vector<uint64_t> nw(mv.size());
+    std::vector<const uint8_t*> src(mv.size());
+    for (size_t m = 0; m < mv.size(); m++) {
+        nw[m] = nwords64(mv[m]->num_bits);
+        src[m] = (const uint8_t*)mv[m]->words;
+        *moved_bytes += lset_slot_bytes(nw[m]);
+    }
+    auto copy = [&]() -> int {
+        if (int rc = lset_stage(ls, nw.data(), nw.size())) return rc;
+        LsetStaged& sg = ls->staged;
+        std::vector<uint8_t*> fresh;
+        for (const auto& ch : sg.fresh) fresh.push_back((uint8_t*)ch->buf.p);
+        std::vector<CopySeg> items;
+        lset_repack_items(sg.pl, ls->chunks.size(), fresh.data(), src.data(), nw.data(), &items);
+        const size_t bytes = items.size() * sizeof(CopySeg);
+        if (int rc = pinned_ensure(ls->pin_retired, &ls->pin, &ls->pin_cap, bytes, "level set")) return rc;
+        memcpy(ls->pin, items.data(), bytes);
+        HIP_TRY(ls->segs.ensure(bytes));
+        HIP_TRY(hipMemcpyAsync(ls->segs.p, ls->pin, bytes, hipMemcpyHostToDevice, st));
+        if (int rc = copy_segs_dev((const CopySeg*)ls->segs.p, items.size(), st)) return rc;
+        HIP_TRY(hipStreamSynchronize(st));  // the edit's one wait: the parent may be closed
+        return LSMB_OK;
+    };
+    if (int rc = copy()) return lset_abandon(ls, st, rc);
+    LsetStaged& sg = ls->staged;
+    for (auto& ch : sg.fresh) ls->chunks.push_back(std::move(ch));
+    sg.fresh.clear();
+    ls->arena = sg.pl.after;  // own_tail: the edit's own add lands in the same chunk
+    for (size_t m = 0; m < mv.size(); m++) {
+        mv[m]->chunk = sg.pl.slot[m].chunk;
+        mv[m]->words = (const uint32_t*)sg.words[m];
+    }
+    return LSMB_OK;
+}
+
+// lsmb_lset_derive (min_ppm == 0: nothing moves, nothing is launched) and
+// lsmb_lset_derive_packed.
+int lset_derive(const lsmb_lset* parent, const uint32_t* drop_ids, uint64_t ndrop, uint32_t min_ppm, uint64_t* dropped,
+                uint64_t* moved, lsmb_lset** out, void* stream) {
     if (out) *out = nullptr;
     if (!parent || !out) return fail(LSMB_EINVAL, "null argument");
     if (!parent->sealed) return fail(LSMB_EINVAL, "derive from an unsealed level set");
     if (ndrop && !drop_ids) return fail(LSMB_EINVAL, "null drop_ids");
+    if (min_ppm > LSMB_LSET_REPACK_ALL)
+        return fail(LSMB_EINVAL, "min_ppm %u: at most 1000000, or LSMB_LSET_REPACK_ALL", min_ppm);
     std::vector<uint32_t> drop(drop_ids, drop_ids + ndrop);
     std::sort(drop.begin(), drop.end());
+    // the surviving tables in derive order: rows 0 .. R-1, then L0 by position
+    std::vector<std::pair<uint32_t, const lsmb_lset::Table*>> surv;
+    uint64_t nd = 0;
+    auto take = [&](uint32_t r, const std::vector<lsmb_lset::Table>& tabs) {
+        for (const auto& T : tabs) {
+            if (std::binary_search(drop.begin(), drop.end(), T.id))
+                nd++;
+            else
+                surv.emplace_back(r, &T);
+        }
+    };
+    for (uint32_t r = 0; r < parent->nrows; r++) take(r, parent->row[r]);
+    take(LSMB_LSET_ROW_L0, parent->l0);
+    // which of them leave their chunk (lset_repack.hpp)
+    std::vector<uint8_t> move(surv.size(), 0), evac;
+    if (min_ppm) {
+        std::vector<RepackTable> rt(surv.size());
+        for (size_t t = 0; t < surv.size(); t++)
+            rt[t] = RepackTable{surv[t].second->chunk, lset_slot_bytes(nwords64(surv[t].second->num_bits))};
+        std::vector<size_t> cap(parent->chunks.size());
+        for (size_t c = 0; c < cap.size(); c++) cap[c] = parent->chunks[c]->buf.bytes;
+        lset_repack_plan(rt.data(), rt.size(), cap.data(), cap.size(), min_ppm, &move, &evac);
+    }
     lsmb_lset* ls = nullptr;
     if (int rc = lsmb_lset_open(parent->c, &ls)) return rc;
-    // the surviving tables, each in its row, and only the chunks that hold one
+    // each survivor in its row (L0: in its relative order), and only the chunks
+    // that hold one that stays
     std::vector<uint32_t> remap(parent->chunks.size(), UINT32_MAX);
-    uint64_t nd = 0;
-    for (uint32_t r = 0; r < parent->nrows; r++)
-        for (const auto& T : parent->row[r]) {
-            if (std::binary_search(drop.begin(), drop.end(), T.id)) {
-                nd++;
-                continue;
-            }
-            if (remap[T.chunk] == UINT32_MAX) {
-                remap[T.chunk] = (uint32_t)ls->chunks.size();
-                ls->chunks.push_back(parent->chunks[T.chunk]);
-            }
-            ls->row[r].push_back(T);
-            ls->row[r].back().chunk = remap[T.chunk];
-            ls->inherited++;
-        }
-    for (const auto& T : parent->l0) {  // the surviving L0 tables keep their relative order
-        if (std::binary_search(drop.begin(), drop.end(), T.id)) {
-            nd++;
+    for (uint32_t r = 0; r < parent->nrows; r++) ls->row[r].reserve(parent->row[r].size());
+    ls->l0.reserve(parent->l0.size());
+    std::vector<lsmb_lset::Table*> mv;  // into the reserved rows: no push below reallocates
+    for (size_t t = 0; t < surv.size(); t++) {
+        const lsmb_lset::Table& T = *surv[t].second;
+        std::vector<lsmb_lset::Table>& into = ls->tables_of(surv[t].first);
+        into.push_back(T);
+        ls->inherited++;
+        if (move[t]) {
+            mv.push_back(&into.back());
             continue;
         }
         if (remap[T.chunk] == UINT32_MAX) {
             remap[T.chunk] = (uint32_t)ls->chunks.size();
             ls->chunks.push_back(parent->chunks[T.chunk]);
         }
-        ls->l0.push_back(T);
-        ls->l0.back().chunk = remap[T.chunk];
-        ls->inherited++;
+        into.back().chunk = remap[T.chunk];
     }
     ls->arena.chunks = ls->chunks.size();  // none of them the child's own: its first add takes a new chunk
     ls->nrows = parent->nrows;
+    uint64_t moved_bytes = 0;
+    if (!mv.empty())
+        if (int rc = lset_repack_moved(ls, mv, stream, &moved_bytes)) {
+            const std::string msg = last_error();
+            lsmb_lset_close(ls);  // all or nothing: the parent is as it was
+            set_last_error(msg);
+            return rc;
+        }
     if (dropped) *dropped = nd;
+    if (moved) moved[0] = mv.size(), moved[1] = moved_bytes;
     *out = ls;
     return LSMB_OK;
+}
+
+}  // namespace
+
+int lsmb_lset_derive(const lsmb_lset* parent, const uint32_t* drop_ids, uint64_t ndrop, uint64_t* dropped,
+                     lsmb_lset** out) {
+    return lset_derive(parent, drop_ids, ndrop, 0, dropped, nullptr, out, nullptr);
+}
+
+// A derive that also moves the survivors of sparse parent chunks into a chunk
+// of the child's own, device to device (k_copy_segs): a chain of edits
+// (src/compaction/scheduler.rs:163-177, src/db/mod.rs:402) then holds a chunk
+// per edit no longer.
+int lsmb_lset_derive_packed(const lsmb_lset* parent, const uint32_t* drop_ids, uint64_t ndrop, uint32_t min_ppm,
+                            uint64_t* dropped, uint64_t moved[2], lsmb_lset** out, void* stream) {
+    return lset_derive(parent, drop_ids, ndrop, min_ppm, dropped, moved, out, stream);
 }
 
 namespace {

@@ -240,6 +240,11 @@ int crc32_dev(lsmb_ctx* c, const uint8_t* d, uint64_t len, uint32_t crc, hipStre
 // in device memory: one launch of k_crc32_seg on st, nothing synchronised.
 struct CrcSeg;
 int crc32_seg_dev(const CrcSeg* d_segs, uint64_t nseg, uint32_t* d_out, hipStream_t st);
+// Every item (source, destination, length) of d_segs, in device memory, moved
+// device to device: one launch of k_copy_segs (lset_repack.hip) on st, nothing
+// synchronised.
+struct CopySeg;
+int copy_segs_dev(const CopySeg* d_segs, uint64_t nseg, hipStream_t st);
 uint32_t crc32_host(const uint8_t* p, uint64_t len, uint32_t crc);
 uint32_t crc32_combine_host(uint32_t crc_a, uint32_t crc_b, uint64_t len_b);
 

@@ -32,6 +32,7 @@ LSMB_ECORRUPT = -4
 LSMB_ENOMEM = -5
 LSMB_LSET_MAX_LEVELS = 8
 LSMB_LSET_NONE = 0xFFFFFFFF  # LevelSet.probe: no table of this row
+LSMB_LSET_REPACK_ALL = 1000001  # LevelSet.derive(repack="all"): every surviving table moves
 LSMB_LSET_ROW_L0 = 0x80000000  # `row` of any LevelSet add: the table goes to the set's L0 part
 LSMB_LSET_L0_MAX = 64
 
@@ -67,6 +68,7 @@ SIGNATURES = {
     "lsmb_crc32_combine": (ctypes.c_uint32, [ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint64]),
     "lsmb_crc32_dev": (ctypes.c_int, [vp, ctypes.c_uint32, vp, ctypes.c_uint64, u32p, vp]),
     "lsmb_crc32_seg_dev": (ctypes.c_int, [vp, vp, ctypes.c_uint64, vp, vp]),
+    "lsmb_copy_segs_dev": (ctypes.c_int, [vp, vp, ctypes.c_uint64, vp]),
     "lsmb_fset_add_crc": (ctypes.c_int, [vp, u8p, ctypes.c_uint64, ctypes.c_uint32, u8p, ctypes.c_uint64, u8p,
                                          ctypes.c_uint64]),
     "lsmb_probe": (ctypes.c_int, [vp, ctypes.POINTER(u64p), u32p, u32p, ctypes.c_uint32, u8p, u64p,
@@ -107,6 +109,8 @@ SIGNATURES = {
                                            u8p, ctypes.c_uint64, u8p, ctypes.c_uint64]),
     "lsmb_lset_seal": (ctypes.c_int, [vp]),
     "lsmb_lset_derive": (ctypes.c_int, [vp, u32p, ctypes.c_uint64, u64p, ctypes.POINTER(vp)]),
+    "lsmb_lset_derive_packed": (ctypes.c_int, [vp, u32p, ctypes.c_uint64, ctypes.c_uint32, u64p, u64p,
+                                               ctypes.POINTER(vp), vp]),
     "lsmb_lset_add_batch": (ctypes.c_int, [vp, ctypes.c_uint64, u32p, u32p, u8p, u64p, u32p, u8p, u64p,
                                            ctypes.POINTER(ctypes.c_int32)]),
     "lsmb_lset_add_batch_dev": (ctypes.c_int, [vp, ctypes.c_uint64, u32p, u32p, vp, u64p, u32p, u32p, u8p, u64p, vp]),
@@ -362,6 +366,13 @@ class Context:
         out an int32 / uint32 device tensor of nseg; asynchronous on stream."""
         _check(lib().lsmb_crc32_seg_dev(self.h, vp(segs.data_ptr()), int(nseg), vp(out.data_ptr()),
                                         self._stream(stream)))
+
+    def copy_segs_dev(self, segs, nseg, stream=None):
+        """nseg device-to-device copies in one launch (lsmb_copy_segs_dev):
+        segs an int64 / uint64 device tensor of (source pointer, destination
+        pointer, byte length) triples, pointers 16-byte aligned, lengths
+        multiples of 16, ranges disjoint; asynchronous on stream."""
+        _check(lib().lsmb_copy_segs_dev(self.h, vp(segs.data_ptr()), int(nseg), self._stream(stream)))
 
     def probe(self, filters, data, offsets=None, key_len=0):
         """filters: [(words uint64 array, num_bits, k)] -> uint8 [n, ceil(F/8)] mask."""
@@ -807,21 +818,43 @@ class LevelSet:
     def seal(self):
         _check(lib().lsmb_lset_seal(self.h))
 
-    def derive(self, drop_ids=()):
+    def derive(self, drop_ids=(), repack=None, stream=None):
         """Version edit (lsmb_lset_derive): a new, unsealed LevelSet holding
         every table of this sealed set whose id is not in drop_ids, sharing
         the device filter words (nothing is uploaded).  Then add / add_many /
         seal; this set and the new one are closed in either order.  The
-        number of tables left out is the new set's `dropped`."""
+        number of tables left out is the new set's `dropped`.
+
+        repack (lsmb_lset_derive_packed): a fraction in (0, 1] moves the
+        survivors of every chunk of this set whose live share is below it into
+        a chunk of the new set's own, device to device on stream (one launch,
+        one wait), and the new set's next add continues there; "all" moves
+        every survivor; 0 moves nothing.  The new set's `moved` is (tables
+        moved, their slot bytes); (0, 0) without repack."""
         ids = np.ascontiguousarray(list(drop_ids), dtype=np.uint32)
         h = vp()
         nd = ctypes.c_uint64()
-        _check(lib().lsmb_lset_derive(self.h, _p(ids, u32p) if ids.size else None, ids.size,
-                                      ctypes.cast(ctypes.byref(nd), u64p), ctypes.byref(h)))
+        mv = np.zeros(2, dtype=np.uint64)
+        if repack is None:
+            _check(lib().lsmb_lset_derive(self.h, _p(ids, u32p) if ids.size else None, ids.size,
+                                          ctypes.cast(ctypes.byref(nd), u64p), ctypes.byref(h)))
+        else:
+            if isinstance(repack, str):
+                if repack != "all":
+                    raise ValueError('derive: repack is None, a fraction in [0, 1] or "all"')
+                ppm = LSMB_LSET_REPACK_ALL
+            else:
+                if not 0 <= repack <= 1:
+                    raise ValueError('derive: repack is None, a fraction in [0, 1] or "all"')
+                ppm = int(round(repack * 1_000_000))
+            _check(lib().lsmb_lset_derive_packed(self.h, _p(ids, u32p) if ids.size else None, ids.size, ppm,
+                                                 ctypes.cast(ctypes.byref(nd), u64p), _p(mv, u64p), ctypes.byref(h),
+                                                 Context._stream(stream)))
         child = LevelSet.__new__(LevelSet)
         child.ctx = self.ctx
         child.h = h
         child.dropped = int(nd.value)
+        child.moved = (int(mv[0]), int(mv[1]))
         return child
 
     def add_many(self, rows, ids, blocks, ranges, crcs=None):
