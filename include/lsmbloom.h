@@ -788,8 +788,9 @@ int lsmb_lset_probe_lists(lsmb_lset* ls, const uint8_t* data, const uint64_t* of
  * checks L0 ranges against each other; an L0 table with min_key > max_key is
  * LSMB_EINVAL naming its id.
  * lsmb_lset_rows, _total_tables, _table_order, lsmb_lset_probe* and
- * lsmb_lset_probe_lists* see the rows only; a set with no L0 table behaves as
- * before.  lsmb_lset_tables(ls, LSMB_LSET_ROW_L0) is the L0 count, and
+ * lsmb_lset_probe_lists* see the rows only (lsmb_lset_probe_version_lists*
+ * below list L0 too); a set with no L0 table behaves as before.
+ * lsmb_lset_tables(ls, LSMB_LSET_ROW_L0) is the L0 count, and
  * lsmb_lset_stats counts L0 tables in [0], [1], [4] and [5] like any other. */
 #define LSMB_LSET_ROW_L0 0x80000000u /* `row` of any add path: the table goes to L0 */
 #define LSMB_LSET_L0_MAX 64
@@ -820,6 +821,66 @@ int lsmb_lset_probe_version_dev(lsmb_lset* ls, const void* d_data, const void* d
  * lsmb_lset_probe (src/db/mod.rs:238-267). */
 int lsmb_lset_probe_version(lsmb_lset* ls, const uint8_t* data, const uint64_t* offsets, uint32_t key_len,
                             uint64_t n, uint64_t* l0_mask, uint32_t* out);
+
+/* ---- a whole Version's answer per table ------------------------------------- */
+/* lsmb_lset_probe_lists* see the rows only.  A reader that works table by table
+ * over the whole walk of DB::get (src/db/mod.rs:238-267, src/db/snapshot.rs:40-69)
+ * wants the L0 tables' lists too, from the same hash.  VERSION ORDINALS: with
+ * T0 = lsmb_lset_l0_tables(ls), R = lsmb_lset_rows(ls), G =
+ * lsmb_lset_total_tables(ls) and V = T0 + G,
+ *   v <  T0  is the L0 table at position v, the numbering of
+ *            lsmb_lset_probe_version's mask bits: a reader walks v = T0-1 .. 0
+ *            for newest first, as src/db/mod.rs:243 does;
+ *   v >= T0  is the rows' ordinal g = v - T0 of lsmb_lset_table_order. */
+
+/* V (src/db/mod.rs:238-267, src/db/snapshot.rs:40-69, src/sstable/reader.rs:192-199:
+ * every table a get may consult).  0 for NULL or an unsealed set. */
+uint64_t lsmb_lset_version_tables(const lsmb_lset* ls);
+
+/* Host outputs: ids[V] = lsmb_lset_l0_order's ids, then lsmb_lset_table_order's;
+ * part_base[R + 2] = 0, T0, T0 + base_1, ..., T0 + base_R = V: the first
+ * Version ordinal of L0, of every row, and the end (the tables of
+ * src/db/mod.rs:238-267's walk, src/db/snapshot.rs:40-69; each checked as
+ * src/sstable/reader.rs:192-199).  Either pointer may be NULL.  Before seal:
+ * LSMB_EINVAL. */
+int lsmb_lset_version_order(const lsmb_lset* ls, uint32_t* ids, uint64_t* part_base);
+
+/* Bytes of device workspace a Version lists probe of n keys needs (the batched
+ * walk of src/db/mod.rs:238-267 / src/db/snapshot.rs:40-69 under
+ * src/sstable/reader.rs:192-199's checks keeps its masks and intermediate
+ * answers there).  0 for NULL, an unsealed set, n == 0, V == 0 or n > 2^32-1;
+ * with T0 == 0 it is lsmb_lset_lists_work_bytes(ls, n). */
+uint64_t lsmb_lset_version_lists_work_bytes(const lsmb_lset* ls, uint64_t n);
+
+/* d_starts is uint64_t[V + 1], d_index is uint32_t[cap].  For every Version
+ * ordinal v, d_index[d_starts[v] .. d_starts[v+1]) = the indices i, ascending,
+ * of the keys with
+ *     min_v <= key i <= max_v && may_contain(filter v, key i)
+ * (src/db/mod.rs:238-267, src/db/snapshot.rs:40-69, src/sstable/reader.rs:192-199):
+ * for v < T0 the keys whose bit v is set in lsmb_lset_probe_version's mask, for
+ * v >= T0 the keys for which lsmb_lset_probe answers that table in its row; one
+ * hash per key serves both.  d_starts[0] = 0, d_starts[T0] = the number of L0
+ * entries, d_starts[V] = the total.  Capacity, counting calls, errors, streams,
+ * scratch and determinism are lsmb_lset_probe_lists_dev's with V for G and
+ * lsmb_lset_version_lists_work_bytes for the workspace: d_starts is always
+ * exact; the entry at global position p is written iff p < cap and nothing else
+ * in d_index is touched; n == 0 or V == 0 writes V + 1 zero starts and nothing
+ * else; LSMB_EINVAL (outputs untouched) for n > 2^32-1, V > 2^32-1, a call
+ * before seal, null outputs, and with n > 0 && V > 0 a null or not
+ * 16-byte-aligned d_work or work_bytes below the need.  With T0 == 0 the call
+ * is lsmb_lset_probe_lists_dev, byte for byte.  No atomics: the same keys give
+ * the same bytes on every run. */
+int lsmb_lset_probe_version_lists_dev(lsmb_lset* ls, const void* d_data, const void* d_offsets, uint32_t key_len,
+                                      uint64_t n, void* d_starts, void* d_index, uint64_t cap, void* d_work,
+                                      uint64_t work_bytes, void* stream);
+
+/* Host keys and host outputs (starts[V + 1], index[cap]); synchronous; the
+ * lists of src/db/mod.rs:238-267's walk (src/db/snapshot.rs:40-69) under
+ * src/sstable/reader.rs:192-199's checks as above.  The workspace is the
+ * context's own scratch, as lsmb_lset_probe_lists; only starts and
+ * min(total, cap) entries cross PCIe on the way back. */
+int lsmb_lset_probe_version_lists(lsmb_lset* ls, const uint8_t* data, const uint64_t* offsets, uint32_t key_len,
+                                  uint64_t n, uint64_t* starts, uint32_t* index, uint64_t cap);
 
 /* ---- introspection ------------------------------------------------------- */
 

@@ -501,6 +501,53 @@ class LevelSet {
                                         stream));
     }
 
+    // The whole Version per table (lsmb_lset_probe_version_lists), keyed by
+    // Version ordinal: v < l0_tables() is the L0 table at position v (walk
+    // them from the highest down for newest first, src/db/mod.rs:243), v >=
+    // l0_tables() the rows' ordinal v - l0_tables().
+    uint64_t version_tables() const { return lsmb_lset_version_tables(ls_); }
+    struct VersionOrder {
+        std::vector<uint32_t> ids;        // version_tables(): l0_order(), then table_order().ids
+        std::vector<uint64_t> part_base;  // rows() + 2: 0, T0, T0 + row_base[1], ..., version_tables()
+    };
+    VersionOrder version_order() const {
+        VersionOrder o;
+        o.ids.resize(version_tables());
+        o.part_base.resize(static_cast<size_t>(rows()) + 2);
+        check(lsmb_lset_version_order(ls_, o.ids.data(), o.part_base.data()));
+        return o;
+    }
+    // index[starts[v] .. starts[v+1]) = the ascending indices of the keys that
+    // table v answers (bit v of probe_version()'s mask, or probe()'s answer in
+    // its row), from one hash per key; starts has version_tables() + 1
+    // entries.  A counting call sizes the index.
+    Lists probe_version_lists(const std::vector<std::string>& keys) {
+        std::vector<uint64_t> offs(keys.size() + 1, 0);
+        std::string data;
+        for (size_t i = 0; i < keys.size(); i++) {
+            data += keys[i];
+            offs[i + 1] = data.size();
+        }
+        Lists out;
+        out.starts.assign(version_tables() + 1, 0);
+        check(lsmb_lset_probe_version_lists(ls_, u8(data), offs.data(), 0, keys.size(), out.starts.data(), nullptr, 0));
+        out.index.resize(out.starts.back());
+        if (!out.index.empty())
+            check(lsmb_lset_probe_version_lists(ls_, u8(data), offs.data(), 0, keys.size(), out.starts.data(),
+                                                out.index.data(), out.index.size()));
+        return out;
+    }
+    // Device keys, outputs (d_starts: version_tables() + 1 uint64_t, d_index:
+    // cap uint32_t) and workspace (version_lists_work_bytes(n) bytes),
+    // asynchronous on `stream`.
+    uint64_t version_lists_work_bytes(uint64_t n) const { return lsmb_lset_version_lists_work_bytes(ls_, n); }
+    void probe_version_lists_dev(const void* d_data, const void* d_offsets, uint32_t key_len, uint64_t n,
+                                 void* d_starts, void* d_index, uint64_t cap, void* d_work, uint64_t work_bytes,
+                                 void* stream = nullptr) {
+        check(lsmb_lset_probe_version_lists_dev(ls_, d_data, d_offsets, key_len, n, d_starts, d_index, cap, d_work,
+                                                work_bytes, stream));
+    }
+
    private:
     explicit LevelSet(lsmb_lset* h) : ls_(h) {}  // derive
     static const uint8_t* u8(std::string_view s) { return reinterpret_cast<const uint8_t*>(s.data()); }

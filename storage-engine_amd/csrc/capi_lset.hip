@@ -1,7 +1,8 @@
 // capi_lset.hip — the C ABI of the level set (lsmb_lset_*, include/lsmbloom.h).
 // Host-side plumbing only; the placement of filters in the arena is planned in
 // lset_arena.hpp, a repacking derive in lset_repack.hpp; the kernels are in
-// lset.hip, lset_lists.hip, lset_repack.hip and crc32.hip.
+// lset.hip, lset_lists.hip, lset_version.hip, lset_version_lists.hip,
+// lset_repack.hip and crc32.hip.
 #include <string.h>
 
 #include <algorithm>
@@ -17,6 +18,7 @@
 #include "lset_lists_plan.hpp"
 #include "lset_order.hpp"
 #include "lset_repack.hpp"
+#include "lset_vlists_plan.hpp"
 
 using namespace lsmb;
 
@@ -919,6 +921,108 @@ int lsmb_lset_probe_lists(lsmb_lset* ls, const uint8_t* data, const uint64_t* of
     HIP_TRY(hipMemcpyAsync(starts, d_starts, (G + 1) * 8, hipMemcpyDeviceToHost, c->st));
     HIP_TRY(hipStreamSynchronize(c->st));
     const uint64_t got = std::min<uint64_t>(starts[G], dcap);
+    if (got) {
+        HIP_TRY(hipMemcpyAsync(index, d_index, got * 4, hipMemcpyDeviceToHost, c->st));
+        HIP_TRY(hipStreamSynchronize(c->st));
+    }
+    return LSMB_OK;
+}
+
+// ------------------------------------------------- a whole Version per table
+// The lists over Version ordinals (src/db/mod.rs:238-267): v < T0 the L0 table
+// at position v, v >= T0 the rows' ordinal v - T0; V = T0 + G.
+uint64_t lsmb_lset_version_tables(const lsmb_lset* ls) {
+    return ls && ls->sealed ? (uint64_t)ls->l0.size() + ls->base[ls->nrows] : 0;
+}
+
+int lsmb_lset_version_order(const lsmb_lset* ls, uint32_t* ids, uint64_t* part_base) {
+    if (int rc = lset_probe_check(ls)) return rc;
+    const uint64_t T0 = ls->l0.size();
+    if (ids) {
+        for (uint64_t j = 0; j < T0; j++) ids[j] = ls->l0[j].id;
+        if (!ls->ids.empty()) memcpy(ids + T0, ls->ids.data(), ls->ids.size() * sizeof(uint32_t));
+    }
+    if (part_base) {
+        part_base[0] = 0;
+        for (uint32_t r = 0; r <= ls->nrows; r++) part_base[1 + r] = T0 + ls->base[r];
+    }
+    return LSMB_OK;
+}
+
+uint64_t lsmb_lset_version_lists_work_bytes(const lsmb_lset* ls, uint64_t n) {
+    if (!ls || !ls->sealed || n > UINT32_MAX) return 0;
+    return lset_vlists_plan(n, (uint32_t)ls->l0.size(), ls->nrows, ls->base[ls->nrows]).work_bytes;
+}
+
+// The argument checks shared by both Version lists entry points.
+static int lset_vlists_check(const lsmb_lset* ls, uint64_t n, const void* starts, const void* index, uint64_t cap) {
+    if (int rc = lset_probe_check(ls)) return rc;
+    if (n > UINT32_MAX) return fail(LSMB_EINVAL, "more than 2^32-1 keys (the lists hold 32-bit indices)");
+    if (ls->l0.size() + ls->base[ls->nrows] > UINT32_MAX) return fail(LSMB_EINVAL, "more than 2^32-1 tables");
+    if (!starts || (cap && !index)) return fail(LSMB_EINVAL, "null output");
+    return LSMB_OK;
+}
+
+static int lset_vlists_launch(lsmb_lset* ls, const KeyBatch& kb, uint64_t* d_starts, uint32_t* d_index, uint64_t cap,
+                              void* d_work, uint64_t work_bytes, hipStream_t st) {
+    HIP_TRY(launch_lset_version_lists(kb, ls->rows, ls->base[ls->nrows], (const RangedFilter*)ls->l0_desc.p,
+                                      (uint32_t)ls->l0.size(), ls->l0_rg, ls->l0_cl, d_starts, d_index, cap, d_work,
+                                      work_bytes, ls->c->num_cus, st));
+    return LSMB_OK;
+}
+
+int lsmb_lset_probe_version_lists_dev(lsmb_lset* ls, const void* d_data, const void* d_offsets, uint32_t key_len,
+                                      uint64_t n, void* d_starts, void* d_index, uint64_t cap, void* d_work,
+                                      uint64_t work_bytes, void* stream) {
+    if (int rc = lset_vlists_check(ls, n, d_starts, d_index, cap)) return rc;
+    if (ls->l0.empty())  // the rows' own lists, byte for byte
+        return lsmb_lset_probe_lists_dev(ls, d_data, d_offsets, key_len, n, d_starts, d_index, cap, d_work, work_bytes,
+                                         stream);
+    const uint64_t V = ls->l0.size() + ls->base[ls->nrows];
+    if (n) {
+        if (!d_data) return fail(LSMB_EINVAL, "null keys");
+        if (!d_work || (reinterpret_cast<uintptr_t>(d_work) & 15))
+            return fail(LSMB_EINVAL, "null or misaligned workspace (16-byte alignment)");
+        const uint64_t need = lsmb_lset_version_lists_work_bytes(ls, n);
+        if (work_bytes < need)
+            return fail(LSMB_EINVAL, "workspace of %llu bytes, lsmb_lset_version_lists_work_bytes asks for %llu",
+                        (unsigned long long)work_bytes, (unsigned long long)need);
+    }
+    DevGuard g(ls->c->dev);
+    const hipStream_t st = pick_stream(ls->c, stream);
+    if (n == 0) {
+        HIP_TRY(hipMemsetAsync(d_starts, 0, (V + 1) * 8, st));
+        return LSMB_OK;
+    }
+    KeyBatch kb{(const uint8_t*)d_data, (const uint64_t*)d_offsets, key_len, n};
+    return lset_vlists_launch(ls, kb, (uint64_t*)d_starts, (uint32_t*)d_index, cap, d_work, work_bytes, st);
+}
+
+int lsmb_lset_probe_version_lists(lsmb_lset* ls, const uint8_t* data, const uint64_t* offsets, uint32_t key_len,
+                                  uint64_t n, uint64_t* starts, uint32_t* index, uint64_t cap) {
+    if (int rc = lset_vlists_check(ls, n, starts, index, cap)) return rc;
+    if (ls->l0.empty()) return lsmb_lset_probe_lists(ls, data, offsets, key_len, n, starts, index, cap);
+    if (n && host_keys_null(data, offsets, key_len, n)) return fail(LSMB_EINVAL, "null keys");
+    const uint64_t V = ls->l0.size() + ls->base[ls->nrows];
+    memset(starts, 0, (V + 1) * 8);
+    if (n == 0) return LSMB_OK;
+    lsmb_ctx* c = ls->c;
+    DevGuard g(c->dev);
+    // the context's output scratch, carved: workspace | starts | index (no
+    // list entry beyond one per L0 table, row and key)
+    const LsetVlistsPlan pl = lset_vlists_plan(n, (uint32_t)ls->l0.size(), ls->nrows, ls->base[ls->nrows]);
+    const uint64_t dcap = std::min<uint64_t>(cap, pl.entries);
+    const uint64_t sbytes = ((V + 1) * 8 + kLlAlign - 1) / kLlAlign * kLlAlign;
+    HIP_TRY(c->out.ensure(pl.work_bytes + sbytes + std::max<uint64_t>(dcap, 1) * 4));
+    uint8_t* w = (uint8_t*)c->out.p;
+    uint64_t* d_starts = (uint64_t*)(w + pl.work_bytes);
+    uint32_t* d_index = (uint32_t*)(w + pl.work_bytes + sbytes);
+    KeyBatch kb;
+    if (int rc = stage_host_keys(c, data, offsets, key_len, n, &kb)) return rc;
+    if (int rc = lset_vlists_launch(ls, kb, d_starts, d_index, dcap, w, pl.work_bytes, c->st)) return rc;
+    HIP_TRY(hipMemcpyAsync(starts, d_starts, (V + 1) * 8, hipMemcpyDeviceToHost, c->st));
+    HIP_TRY(hipStreamSynchronize(c->st));
+    const uint64_t got = std::min<uint64_t>(starts[V], dcap);
     if (got) {
         HIP_TRY(hipMemcpyAsync(index, d_index, got * 4, hipMemcpyDeviceToHost, c->st));
         HIP_TRY(hipStreamSynchronize(c->st));

@@ -12,7 +12,9 @@
 //                    + its rank among the wave's set lanes (mbcnt)
 // Positions follow from counts alone (no atomics), tiles and chunks are
 // contiguous and ranks ordered, so every slot's list is ascending and the
-// output is the same on every run.
+// output is the same on every run.  Tile size and scratch bytes:
+// fset_lists_plan.hpp.
+#include "fset_lists_plan.hpp"
 #include "kernels.hpp"
 
 namespace lsmb {
@@ -202,11 +204,6 @@ hipError_t lists_with(const Row* rows, uint64_t n, uint64_t live, uint32_t nlive
 }
 
 }  // namespace
-
-uint64_t fset_lists_tile_bytes(uint64_t n, uint64_t live) {
-    const uint64_t ntiles = (n + kListTile - 1) / kListTile;
-    return (uint64_t)__builtin_popcountll(live) * ((ntiles + 3) & ~3ull) * 4;
-}
 
 hipError_t launch_fset_lists(const uint8_t* d_rows, uint32_t row_bytes, uint64_t n, uint64_t live, uint32_t* d_tiles,
                              uint64_t* d_starts, uint32_t* d_index, uint64_t cap, hipStream_t st, hipEvent_t done) {

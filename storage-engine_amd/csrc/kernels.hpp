@@ -6,6 +6,7 @@
 #include <stdint.h>
 
 #include "bloom_math.hpp"
+#include "fset_lists_plan.hpp"
 #include "fset_types.hpp"
 
 namespace lsmb {
@@ -173,8 +174,7 @@ hipError_t launch_fset_probe(const KeyBatch& kb, const RangedFilter* d_filters, 
 // at position p is stored iff p < cap.  d_tiles: fset_lists_tile_bytes(n,
 // live) bytes of scratch (per-tile counts, then offsets), 16-B aligned.
 // 1 <= n <= 2^32-1, live != 0.  done: completed by the last kernel.
-constexpr uint32_t kListTile = 1024;  // keys per workgroup
-uint64_t fset_lists_tile_bytes(uint64_t n, uint64_t live);
+// (kListTile and fset_lists_tile_bytes: fset_lists_plan.hpp)
 hipError_t launch_fset_lists(const uint8_t* d_rows, uint32_t row_bytes, uint64_t n, uint64_t live, uint32_t* d_tiles,
                              uint64_t* d_starts, uint32_t* d_index, uint64_t cap, hipStream_t st,
                              hipEvent_t done = nullptr);
@@ -227,6 +227,15 @@ hipError_t launch_lset_version(const KeyBatch& kb, const LsetRows& rows, const R
                                const FsetRanges& rg, const FsetClasses& cl, uint64_t* d_l0_mask, uint32_t* d_out,
                                int num_cus, hipStream_t st);
 
+// The same kernel feeding the Version lists probe: the L0 masks in n rows of
+// row_bytes (1, 2, 4 or 8, covering nl0) at d_mask_rows, as launch_fset_probe
+// leaves them for launch_fset_lists, and the rows answered by ordinal at
+// d_out[r * stride + i] as launch_lset_probe_ordinals does; stride >= kb.n.
+hipError_t launch_lset_version_ordinals(const KeyBatch& kb, const LsetRows& rows, const RangedFilter* d_l0,
+                                        uint32_t nl0, const FsetRanges& rg, const FsetClasses& cl, uint8_t* d_mask_rows,
+                                        uint32_t row_bytes, uint32_t* d_out, uint64_t stride, int num_cus,
+                                        hipStream_t st);
+
 // The level set's answer per table (lset_lists.hip): with G = the tables of
 // all rows, for every ordinal g < G, d_index[d_starts[g] .. d_starts[g+1]) =
 // the ascending key indices i whose row answers table g; d_starts[G + 1] is
@@ -237,6 +246,30 @@ hipError_t launch_lset_version(const KeyBatch& kb, const LsetRows& rows, const R
 hipError_t launch_lset_lists(const KeyBatch& kb, const LsetRows& rows, uint64_t G, uint64_t* d_starts,
                              uint32_t* d_index, uint64_t cap, void* d_work, uint64_t work_bytes, int num_cus,
                              hipStream_t st);
+
+// launch_lset_lists after its ordinal probe: splits the answers already in the
+// kAns region of d_work (laid out by pl = lset_lists_plan(n, R, G), n * R * G
+// > 0) into lists that begin at *d_base (device memory, read by the kernels;
+// NULL = 0) and at d_starts[ord_off]: d_starts[ord_off + g] = *d_base + the
+// start of ordinal g's list, g <= G, and the entry at position p of the lists
+// goes to d_index[*d_base + p] iff *d_base + p < cap.  With a null base and
+// ord_off = 0 this is the second half of launch_lset_lists exactly.
+struct LsetListsPlan;
+hipError_t launch_lset_lists_split(const LsetListsPlan& pl, void* d_work, const uint64_t* d_base, uint64_t ord_off,
+                                   uint64_t* d_starts, uint32_t* d_index, uint64_t cap, int num_cus, hipStream_t st);
+
+// A whole Version per table (lset_version_lists.hip): Version ordinal v < nl0
+// is the L0 table at position v, v >= nl0 the rows' ordinal v - nl0, V = nl0 +
+// G.  d_index[d_starts[v] .. d_starts[v+1]) = the ascending key indices that
+// table v answers, from one hash per key; d_starts[V + 1] is always exact, the
+// entry at position p is stored iff p < cap.  All scratch is d_work (16-B
+// aligned, at least lset_vlists_plan(kb.n, nl0, rows.nrows, G).work_bytes, see
+// lset_vlists_plan.hpp).  1 <= kb.n <= 2^32-1, 1 <= nl0 <= 64, G <= 2^32-1.
+// No host synchronisation.
+hipError_t launch_lset_version_lists(const KeyBatch& kb, const LsetRows& rows, uint64_t G, const RangedFilter* d_l0,
+                                     uint32_t nl0, const FsetRanges& rg, const FsetClasses& cl, uint64_t* d_starts,
+                                     uint32_t* d_index, uint64_t cap, void* d_work, uint64_t work_bytes, int num_cus,
+                                     hipStream_t st);
 
 // A kernel launch whose completion also completes `done` (when non-null):
 // hipExtLaunchKernelGGL tracks the event with the dispatch's own completion

@@ -23,6 +23,12 @@
 // same bytes on every run.  From the second pass on the element count E is
 // known to the device only: the grid is sized for R * n and tiles past E leave
 // at once.  Geometry and workspace layout: lset_lists_plan.hpp.
+//
+// launch_lset_lists = the ordinal probe, then launch_lset_lists_split (the
+// passes and the bounds).  The Version lists probe (lset_version_lists.hip)
+// fills the answer rows from its own fused kernel and enters at the split,
+// with the lists based behind its L0 lists: a base for the last scatter and
+// for the bounds, read from device memory (null = 0, the rows' own probe).
 #include "kernels.hpp"
 #include "lset_lists_plan.hpp"
 
@@ -187,13 +193,15 @@ __global__ __launch_bounds__(kLlBlock) void k_ll_rowscan(uint64_t* __restrict__ 
 
 // out_keys[p] = key, out_vals[p] = value for every element of the tile, p as
 // the file comment states it.  The last pass stores the values (key indices)
-// into the caller's index under its capacity; `limit` (R * n, the buffers'
-// size) bounds every other store.
+// into the caller's index under its capacity, the lists beginning at *base
+// there (null: 0; the Version lists probe puts them behind the L0 lists);
+// `limit` (R * n, the buffers' size) bounds every other store.
 template <bool kFirst, bool kLast>
 __global__ __launch_bounds__(kLlBlock) void k_ll_scatter(LlSrc s, uint32_t shift, uint32_t ntiles,
                                                          const uint64_t* __restrict__ offs,
                                                          uint32_t* __restrict__ out_keys,
-                                                         uint32_t* __restrict__ out_vals, uint64_t limit, uint64_t cap) {
+                                                         uint32_t* __restrict__ out_vals, uint64_t limit, uint64_t cap,
+                                                         const uint64_t* __restrict__ base) {
     __shared__ uint32_t wcnt[kLlWaves][kLlDigits];
     __shared__ uint64_t wbase[kLlWaves][kLlDigits];
     const uint32_t tile = blockIdx.x, wave = threadIdx.x >> 6;
@@ -211,42 +219,51 @@ __global__ __launch_bounds__(kLlBlock) void k_ll_scatter(LlSrc s, uint32_t shift
         b += wcnt[w][threadIdx.x];
     }
     __syncthreads();
-    const uint64_t vlimit = kLast ? (cap < limit ? cap : limit) : limit;
+    const uint64_t b0 = kLast && base ? *base : 0;  // uniform
+    const uint64_t vcap = kLast ? cap : ~0ull;
 #pragma unroll
     for (uint32_t k = 0; k < kLlChunks; k++) {
         if ((pk[k] >> 8) & 1) {
             const uint64_t p = wbase[wave][pk[k] & (kLlDigits - 1)] + (pk[k] >> 9);
-            if (p < limit) out_keys[p] = key[k];
-            if (p < vlimit) out_vals[p] = val[k];
+            if (p < limit) {
+                out_keys[p] = key[k];
+                if (b0 + p < vcap) out_vals[b0 + p] = val[k];
+            }
         }
     }
 }
 
 // starts[g] = the first position whose ordinal is >= g: position q fills every
 // g in (skeys[q-1], skeys[q]] (from 0 at q = 0, to G at q = E), so the tables
-// of a gap — empty ones — get equal starts.
+// of a gap — empty ones — get equal starts.  The lists begin at *base (null:
+// 0) of the index and at `off` of starts: starts[off + g] = *base + q.
 __global__ __launch_bounds__(256) void k_ll_bounds(const uint32_t* __restrict__ skeys, const uint64_t* __restrict__ count,
-                                                   uint64_t G, uint64_t* __restrict__ starts) {
+                                                   uint64_t G, uint64_t* __restrict__ starts,
+                                                   const uint64_t* __restrict__ base, uint64_t off) {
     const uint64_t E = *count;
+    const uint64_t b0 = base ? *base : 0;
+    starts += off;
     const uint64_t gs = (uint64_t)gridDim.x * blockDim.x;
     for (uint64_t q = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; q <= E; q += gs) {
         const uint64_t lo = q ? (uint64_t)skeys[q - 1] + 1 : 0;
         uint64_t hi = q < E ? skeys[q] : G;
         if (hi > G) hi = G;
-        for (uint64_t g = lo; g <= hi; g++) starts[g] = q;
+        for (uint64_t g = lo; g <= hi; g++) starts[g] = b0 + q;
     }
 }
 
 template <bool kFirst, bool kLast>
 hipError_t ll_pass(const LlSrc& s, uint32_t shift, uint32_t ntiles, uint64_t* counts, uint64_t* meta,
-                   uint32_t* out_keys, uint32_t* out_vals, uint64_t limit, uint64_t cap, hipStream_t st) {
+                   uint32_t* out_keys, uint32_t* out_vals, uint64_t limit, uint64_t cap, const uint64_t* base,
+                   hipStream_t st) {
     k_ll_hist<kFirst><<<ntiles, kLlBlock, 0, st>>>(s, shift, ntiles, counts);
     if (hipError_t e = hipGetLastError(); e != hipSuccess) return e;
     k_ll_rowsum<<<kLlDigits, kLlBlock, 0, st>>>(counts, ntiles, meta);
     if (hipError_t e = hipGetLastError(); e != hipSuccess) return e;
     k_ll_rowscan<<<kLlDigits, kLlBlock, 0, st>>>(counts, ntiles, meta, kFirst ? meta + kLlDigits : nullptr);
     if (hipError_t e = hipGetLastError(); e != hipSuccess) return e;
-    k_ll_scatter<kFirst, kLast><<<ntiles, kLlBlock, 0, st>>>(s, shift, ntiles, counts, out_keys, out_vals, limit, cap);
+    k_ll_scatter<kFirst, kLast><<<ntiles, kLlBlock, 0, st>>>(s, shift, ntiles, counts, out_keys, out_vals, limit, cap,
+                                                             base);
     return hipGetLastError();
 }
 
@@ -260,6 +277,16 @@ hipError_t launch_lset_lists(const KeyBatch& kb, const LsetRows& rows, uint64_t 
     if (!d_starts || (cap && !d_index)) return hipErrorInvalidValue;
     const LsetListsPlan pl = lset_lists_plan(kb.n, rows.nrows, G);
     if (!d_work || (reinterpret_cast<uintptr_t>(d_work) & 15) || work_bytes < pl.work_bytes) return hipErrorInvalidValue;
+    uint32_t* ans = (uint32_t*)((uint8_t*)d_work + pl.reg[LsetListsPlan::kAns].off);
+    if (hipError_t e = launch_lset_probe_ordinals(kb, rows, ans, pl.row_stride, num_cus, st); e != hipSuccess) return e;
+    return launch_lset_lists_split(pl, d_work, nullptr, 0, d_starts, d_index, cap, num_cus, st);
+}
+
+hipError_t launch_lset_lists_split(const LsetListsPlan& pl, void* d_work, const uint64_t* d_base, uint64_t ord_off,
+                                   uint64_t* d_starts, uint32_t* d_index, uint64_t cap, int num_cus, hipStream_t st) {
+    if (pl.work_bytes == 0 || !d_work || (reinterpret_cast<uintptr_t>(d_work) & 15)) return hipErrorInvalidValue;
+    if (!d_starts || (cap && !d_index)) return hipErrorInvalidValue;
+    const uint64_t G = pl.G;
     uint8_t* w = (uint8_t*)d_work;
     uint64_t* meta = (uint64_t*)(w + pl.reg[LsetListsPlan::kMeta].off);
     uint64_t* counts = (uint64_t*)(w + pl.reg[LsetListsPlan::kCounts].off);
@@ -269,12 +296,10 @@ hipError_t launch_lset_lists(const KeyBatch& kb, const LsetRows& rows, uint64_t 
     uint32_t* val_b = (uint32_t*)(w + pl.reg[LsetListsPlan::kValB].off);
     const uint32_t ntiles = (uint32_t)pl.ntiles;  // <= 8 * 2^21
 
-    if (hipError_t e = launch_lset_probe_ordinals(kb, rows, ans, pl.row_stride, num_cus, st); e != hipSuccess) return e;
-
     const uint64_t* count = meta + kLlDigits;
     // pass 0 reads the answers and writes buffer a; then a -> b (b's keys take
     // the answers' place) -> a ...; the last pass's values are the index
-    LlSrc s{ans, nullptr, count, kb.n, pl.row_stride, (uint32_t)pl.tiles_per_row};
+    LlSrc s{ans, nullptr, count, pl.n, pl.row_stride, (uint32_t)pl.tiles_per_row};
     uint32_t* sorted = nullptr;
     for (uint32_t p = 0; p < pl.passes; p++) {
         const bool first = p == 0, last = p + 1 == pl.passes, to_a = (p & 1) == 0;
@@ -282,10 +307,10 @@ hipError_t launch_lset_lists(const KeyBatch& kb, const LsetRows& rows, uint64_t 
         uint32_t* ov = last ? d_index : (to_a ? val_a : val_b);
         const uint32_t shift = p * kLlRadixBits;
         hipError_t e;
-        if (first && last) e = ll_pass<true, true>(s, shift, ntiles, counts, meta, ok, ov, pl.pairs, cap, st);
-        else if (first) e = ll_pass<true, false>(s, shift, ntiles, counts, meta, ok, ov, pl.pairs, cap, st);
-        else if (last) e = ll_pass<false, true>(s, shift, ntiles, counts, meta, ok, ov, pl.pairs, cap, st);
-        else e = ll_pass<false, false>(s, shift, ntiles, counts, meta, ok, ov, pl.pairs, cap, st);
+        if (first && last) e = ll_pass<true, true>(s, shift, ntiles, counts, meta, ok, ov, pl.pairs, cap, d_base, st);
+        else if (first) e = ll_pass<true, false>(s, shift, ntiles, counts, meta, ok, ov, pl.pairs, cap, d_base, st);
+        else if (last) e = ll_pass<false, true>(s, shift, ntiles, counts, meta, ok, ov, pl.pairs, cap, d_base, st);
+        else e = ll_pass<false, false>(s, shift, ntiles, counts, meta, ok, ov, pl.pairs, cap, d_base, st);
         if (e != hipSuccess) return e;
         s.keys = ok;
         s.vals = ov;
@@ -294,7 +319,7 @@ hipError_t launch_lset_lists(const KeyBatch& kb, const LsetRows& rows, uint64_t 
     uint64_t g = (pl.pairs + 1 + 255) / 256;
     const uint64_t gmax = (uint64_t)num_cus * 8;
     if (g > gmax) g = gmax;
-    k_ll_bounds<<<dim3((uint32_t)g), dim3(256), 0, st>>>(sorted, count, G, d_starts);
+    k_ll_bounds<<<dim3((uint32_t)g), dim3(256), 0, st>>>(sorted, count, G, d_starts, d_base, ord_off);
     return hipGetLastError();
 }
 

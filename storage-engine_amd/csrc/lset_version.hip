@@ -15,7 +15,8 @@
 //         table at position j, so a reader visits set bits from the highest
 //         down (version.level(0).iter().rev());
 //   rows  the walk of lset.hip (lset_rows_walk), ids stored as k_lset_probe
-//         stores them.
+//         stores them (or ordinals, as k_lset_probe's ordinal form does, for
+//         the Version lists probe).
 // csrc/fset_plan.hpp states the L0 answer in plain C++ (fset_plan_answer),
 // csrc/lset_order.hpp the rows' search (lset_find).
 #include <type_traits>
@@ -38,10 +39,16 @@ using ks::VarLen;
 // tables at most twice.  The row search adds no register beyond that cap's 64
 // (16-B keys) and 128: no scratch in any instantiation (DESIGN.md section 4.4
 // records the compiled figures).
-template <class Src>
+//
+// kOrdinal = false: the Version probe itself, 8-byte masks and table ids at
+// out[r * n + i].  kOrdinal = true, for the Version lists probe
+// (lset_version_lists.hip): masks in rows of rb bytes (1, 2, 4 or 8, covering
+// nl0; a wave-uniform choice inside MaskOut::put, so one instantiation per key
+// source serves every width) and the rows' ordinals at out[r * stride + i].
+template <class Src, bool kOrdinal>
 __global__ __launch_bounds__(kClassBlock, 4 * class_wgs_per_cu<Src>()) void k_lset_version(
     Src src, uint64_t n, LsetRows rows, const RangedFilter* __restrict__ l0, uint32_t nl0, FsetRanges rg,
-    FsetClasses cl, uint64_t* __restrict__ mask, uint32_t* __restrict__ out) {
+    FsetClasses cl, uint8_t* __restrict__ mask, uint32_t rb, uint32_t* __restrict__ out, uint64_t stride) {
     extern __shared__ __align__(16) uint8_t smem_raw[];
     __shared__ FsetClassLds S;
     __shared__ FsetLds L;
@@ -50,7 +57,7 @@ __global__ __launch_bounds__(kClassBlock, 4 * class_wgs_per_cu<Src>()) void k_ls
     __syncthreads();
     build_class_tables(cl, S, smem_raw);
     __syncthreads();
-    const MaskOut mo{reinterpret_cast<uint8_t*>(mask), 8};
+    const MaskOut mo{mask, kOrdinal ? rb : 8u};
     const uint32_t npts = rg.npts;
     const uint64_t gs = (uint64_t)gridDim.x * blockDim.x;
     for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gs) {
@@ -61,22 +68,43 @@ __global__ __launch_bounds__(kClassBlock, 4 * class_wgs_per_cu<Src>()) void k_ls
         const uint64_t rm = L.regmask[key_region(kx, kp, kl, L, npts)];
         // descriptor d is the L0 table at position d: the descriptor bits are the answer
         mo.put(i, classes_answer(h, rm, cl, S, smem_raw));
-        lset_rows_walk<false>(h, kx, kp, kl, rows, out, n, i);
+        lset_rows_walk<kOrdinal>(h, kx, kp, kl, rows, out, kOrdinal ? stride : n, i);
     }
 }
 
-template <class Src>
+template <class Src, bool kOrdinal>
 hipError_t lset_version_with(const Src& src, uint64_t n, const LsetRows& rows, const RangedFilter* d_l0, uint32_t nl0,
-                             const FsetRanges& rg, const FsetClasses& cl, uint64_t* d_mask, uint32_t* d_out,
-                             int num_cus, hipStream_t st) {
+                             const FsetRanges& rg, const FsetClasses& cl, uint8_t* d_mask, uint32_t rb, uint32_t* d_out,
+                             uint64_t stride, int num_cus, hipStream_t st) {
     uint64_t g = (n + kClassBlock - 1) / kClassBlock;
     const uint64_t gmax = (uint64_t)num_cus * class_wgs_per_cu<Src>();
     if (g > gmax) g = gmax;
     const size_t smem = cl.table_bytes;
-    hipFuncSetAttribute((const void*)k_lset_version<Src>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
-    k_lset_version<Src><<<dim3((uint32_t)g), dim3(kClassBlock), smem, st>>>(src, n, rows, d_l0, nl0, rg, cl, d_mask,
-                                                                              d_out);
+    hipFuncSetAttribute((const void*)k_lset_version<Src, kOrdinal>, hipFuncAttributeMaxDynamicSharedMemorySize,
+                        (int)smem);
+    k_lset_version<Src, kOrdinal><<<dim3((uint32_t)g), dim3(kClassBlock), smem, st>>>(src, n, rows, d_l0, nl0, rg, cl,
+                                                                                        d_mask, rb, d_out, stride);
     return hipGetLastError();
+}
+
+// The argument checks and the choice of key source both forms share.
+template <bool kOrdinal>
+hipError_t lset_version_any(const KeyBatch& kb, const LsetRows& rows, const RangedFilter* d_l0, uint32_t nl0,
+                            const FsetRanges& rg, const FsetClasses& cl, uint8_t* d_mask, uint32_t rb, uint32_t* d_out,
+                            uint64_t stride, int num_cus, hipStream_t st) {
+    if (kb.n == 0) return hipSuccess;
+    if (rows.nrows > kLsetMaxRows || nl0 == 0 || nl0 > 64 || rg.npts > kFsetMaxPoints || cl.ncls > kFsetMaxClasses ||
+        cl.table_bytes > kFsetTableBytes)
+        return hipErrorInvalidValue;
+    if (!d_mask || (rows.nrows && !d_out)) return hipErrorInvalidValue;
+    if (kb.offsets)
+        return lset_version_with<VarLen, kOrdinal>(VarLen{kb.data, kb.offsets}, kb.n, rows, d_l0, nl0, rg, cl, d_mask,
+                                                   rb, d_out, stride, num_cus, st);
+    if (kb.key_len == 16 && (reinterpret_cast<uintptr_t>(kb.data) & 15) == 0)
+        return lset_version_with<Fixed16, kOrdinal>(Fixed16{reinterpret_cast<const uint4*>(kb.data)}, kb.n, rows, d_l0,
+                                                    nl0, rg, cl, d_mask, rb, d_out, stride, num_cus, st);
+    return lset_version_with<FixedN, kOrdinal>(FixedN{kb.data, kb.key_len}, kb.n, rows, d_l0, nl0, rg, cl, d_mask, rb,
+                                               d_out, stride, num_cus, st);
 }
 
 }  // namespace
@@ -84,18 +112,18 @@ hipError_t lset_version_with(const Src& src, uint64_t n, const LsetRows& rows, c
 hipError_t launch_lset_version(const KeyBatch& kb, const LsetRows& rows, const RangedFilter* d_l0, uint32_t nl0,
                                const FsetRanges& rg, const FsetClasses& cl, uint64_t* d_l0_mask, uint32_t* d_out,
                                int num_cus, hipStream_t st) {
-    if (kb.n == 0) return hipSuccess;
-    if (rows.nrows > kLsetMaxRows || nl0 == 0 || nl0 > 64 || rg.npts > kFsetMaxPoints || cl.ncls > kFsetMaxClasses ||
-        cl.table_bytes > kFsetTableBytes)
-        return hipErrorInvalidValue;
-    if (!d_l0_mask || (rows.nrows && !d_out)) return hipErrorInvalidValue;
-    if (kb.offsets)
-        return lset_version_with(VarLen{kb.data, kb.offsets}, kb.n, rows, d_l0, nl0, rg, cl, d_l0_mask, d_out, num_cus,
-                                 st);
-    if (kb.key_len == 16 && (reinterpret_cast<uintptr_t>(kb.data) & 15) == 0)
-        return lset_version_with(Fixed16{reinterpret_cast<const uint4*>(kb.data)}, kb.n, rows, d_l0, nl0, rg, cl,
-                                 d_l0_mask, d_out, num_cus, st);
-    return lset_version_with(FixedN{kb.data, kb.key_len}, kb.n, rows, d_l0, nl0, rg, cl, d_l0_mask, d_out, num_cus, st);
+    return lset_version_any<false>(kb, rows, d_l0, nl0, rg, cl, reinterpret_cast<uint8_t*>(d_l0_mask), 8, d_out, kb.n,
+                                   num_cus, st);
+}
+
+hipError_t launch_lset_version_ordinals(const KeyBatch& kb, const LsetRows& rows, const RangedFilter* d_l0,
+                                        uint32_t nl0, const FsetRanges& rg, const FsetClasses& cl, uint8_t* d_mask_rows,
+                                        uint32_t row_bytes, uint32_t* d_out, uint64_t stride, int num_cus,
+                                        hipStream_t st) {
+    if (row_bytes != 1 && row_bytes != 2 && row_bytes != 4 && row_bytes != 8) return hipErrorInvalidValue;
+    if (row_bytes < 8 && nl0 > 8 * row_bytes) return hipErrorInvalidValue;
+    if (stride < kb.n) return hipErrorInvalidValue;
+    return lset_version_any<true>(kb, rows, d_l0, nl0, rg, cl, d_mask_rows, row_bytes, d_out, stride, num_cus, st);
 }
 
 }  // namespace lsmb

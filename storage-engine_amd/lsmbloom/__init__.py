@@ -130,6 +130,13 @@ SIGNATURES = {
     "lsmb_lset_l0_order": (ctypes.c_int, [vp, u32p]),
     "lsmb_lset_probe_version_dev": (ctypes.c_int, [vp, vp, vp, ctypes.c_uint32, ctypes.c_uint64, vp, vp, vp]),
     "lsmb_lset_probe_version": (ctypes.c_int, [vp, u8p, u64p, ctypes.c_uint32, ctypes.c_uint64, u64p, u32p]),
+    "lsmb_lset_version_tables": (ctypes.c_uint64, [vp]),
+    "lsmb_lset_version_order": (ctypes.c_int, [vp, u32p, u64p]),
+    "lsmb_lset_version_lists_work_bytes": (ctypes.c_uint64, [vp, ctypes.c_uint64]),
+    "lsmb_lset_probe_version_lists_dev": (ctypes.c_int, [vp, vp, vp, ctypes.c_uint32, ctypes.c_uint64, vp, vp,
+                                                         ctypes.c_uint64, vp, ctypes.c_uint64, vp]),
+    "lsmb_lset_probe_version_lists": (ctypes.c_int, [vp, u8p, u64p, ctypes.c_uint32, ctypes.c_uint64, u64p, u32p,
+                                                     ctypes.c_uint64]),
     "lsmb_build_strategy": (ctypes.c_char_p, [ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint64]),
     "lsmb_host_max_keys": (ctypes.c_uint64, []),
     "lsmb_build_sweeps": (ctypes.c_int, [ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint64]),
@@ -1079,6 +1086,76 @@ class LevelSet:
         _check(lib().lsmb_lset_probe_lists_dev(self.h, vp(data.data_ptr()), offs, key_len, n, vp(starts.data_ptr()),
                                                vp(index.data_ptr()) if cap else None, cap,
                                                vp(work.data_ptr()) if wb else None, wb, Context._stream(stream)))
+
+    def version_tables(self):
+        """L0 tables + tables of all rows (0 before seal): the Version lists'
+        ordinals are 0 .. version_tables() - 1, L0 positions first."""
+        return int(lib().lsmb_lset_version_tables(self.h))
+
+    def version_order(self):
+        """-> (ids uint32[V], part_base uint64[rows() + 2]): l0_order()'s ids
+        then table_order()'s; part_base = 0, T0, T0 + row_base[1], ..., V."""
+        ids = np.zeros(max(self.version_tables(), 1), dtype=np.uint32)
+        base = np.zeros(self.rows() + 2, dtype=np.uint64)
+        _check(lib().lsmb_lset_version_order(self.h, _p(ids, u32p), _p(base, u64p)))
+        return ids[:self.version_tables()], base
+
+    def version_lists_work_bytes(self, n):
+        """Bytes of device workspace probe_version_lists_dev needs for n keys."""
+        return int(lib().lsmb_lset_version_lists_work_bytes(self.h, int(n)))
+
+    def probe_version_lists(self, data, offsets=None, key_len=0, cap=None):
+        """Packed host keys (as probe) -> (starts uint64[V + 1], index
+        uint32[min(total, cap)]) over Version ordinals (version_order()):
+        index[starts[v]:starts[v+1]] = the ascending indices of the keys with
+        bit v of probe_version()'s mask set (v < l0_tables()), or for which
+        probe() answers the row table of ordinal v - l0_tables(), from one
+        hash per key (lsmb_lset_probe_version_lists).  cap=None sizes index
+        from a counting call."""
+        data = np.ascontiguousarray(data, dtype=np.uint8).reshape(-1)
+        if offsets is not None:
+            offsets = np.ascontiguousarray(offsets, dtype=np.uint64)
+            n = offsets.size - 1
+            op = _p(offsets, u64p)
+        else:
+            n = data.size // key_len if key_len else 0
+            op = None
+        if data.size == 0:
+            data = np.zeros(1, np.uint8)
+        starts = np.zeros(self.version_tables() + 1, dtype=np.uint64)
+        if cap is None:
+            _check(lib().lsmb_lset_probe_version_lists(self.h, _p(data, u8p), op, key_len, n, _p(starts, u64p), None, 0))
+            cap = int(starts[-1])
+            if cap == 0:
+                return starts, np.zeros(0, dtype=np.uint32)
+        cap = int(cap)
+        index = np.empty(max(cap, 1), dtype=np.uint32)
+        _check(lib().lsmb_lset_probe_version_lists(self.h, _p(data, u8p), op, key_len, n, _p(starts, u64p),
+                                                   _p(index, u32p) if cap else None, cap))
+        return starts, index[:min(int(starts[-1]), cap)]
+
+    def probe_version_lists_keys(self, keys):
+        """list of bytes -> (starts, index) as probe_version_lists."""
+        lens = np.array([len(k) for k in keys], dtype=np.uint64)
+        offs = np.zeros(len(keys) + 1, dtype=np.uint64)
+        np.cumsum(lens, out=offs[1:])
+        return self.probe_version_lists(np.frombuffer(b"".join(bytes(k) for k in keys), dtype=np.uint8), offs)
+
+    def probe_version_lists_dev(self, data, n, starts, index, work, offsets=None, key_len=0, stream=None):
+        """Device keys -> device lists (lsmb_lset_probe_version_lists_dev):
+        starts an int64 / uint64 tensor of version_tables() + 1, index an int32
+        / uint32 tensor whose length is the capacity (None: a counting call),
+        work a uint8 tensor of at least version_lists_work_bytes(n) bytes — the
+        probe's only scratch, so probes on different streams take different
+        tensors.  starts is always exact; entries at and past the capacity are
+        not written."""
+        offs = vp(offsets.data_ptr()) if offsets is not None else None
+        cap = int(index.numel()) if index is not None else 0
+        wb = int(work.numel() * work.element_size()) if work is not None else 0
+        _check(lib().lsmb_lset_probe_version_lists_dev(self.h, vp(data.data_ptr()), offs, key_len, n,
+                                                       vp(starts.data_ptr()), vp(index.data_ptr()) if cap else None, cap,
+                                                       vp(work.data_ptr()) if wb else None, wb,
+                                                       Context._stream(stream)))
 
 
 def build_strategy(num_bits, n, k=7):
