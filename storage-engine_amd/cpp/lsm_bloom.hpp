@@ -48,6 +48,39 @@ inline int check(int rc) {
     throw GpuError(rc, msg);
 }
 
+namespace detail {
+
+// Keys back to back and their keys.size() + 1 offsets: the C ABI's var-length batch.
+struct PackedKeys {
+    std::string data;
+    std::vector<uint64_t> offs;
+    const uint8_t* bytes() const { return reinterpret_cast<const uint8_t*>(data.data()); }
+};
+inline PackedKeys pack_keys(const std::vector<std::string>& keys) {
+    PackedKeys p;
+    p.offs.assign(keys.size() + 1, 0);
+    for (size_t i = 0; i < keys.size(); i++) {
+        p.data += keys[i];
+        p.offs[i + 1] = p.data.size();
+    }
+    return p;
+}
+
+// Table t's min_key and max_key at koff[2t .. 2t + 2] of kb (never empty), as the batch adds take them.
+template <class Range>
+void pack_ranges(const std::vector<Range>& ranges, std::vector<uint8_t>* kb, std::vector<uint64_t>* koff) {
+    koff->assign(2 * ranges.size() + 1, 0);
+    for (size_t t = 0; t < ranges.size(); t++) {
+        kb->insert(kb->end(), ranges[t].min_key.begin(), ranges[t].min_key.end());
+        (*koff)[2 * t + 1] = kb->size();
+        kb->insert(kb->end(), ranges[t].max_key.begin(), ranges[t].max_key.end());
+        (*koff)[2 * t + 2] = kb->size();
+    }
+    kb->push_back(0);
+}
+
+}  // namespace detail
+
 // One GPU (lsmb_ctx).  Movable, not copyable.
 class Context {
    public:
@@ -80,18 +113,14 @@ class Context {
         const size_t ntab = num_bits.size();
         if (seg.size() != ntab + 1 || num_hashes.size() != ntab)
             throw std::invalid_argument("build_batch_blocks: seg needs ntab + 1 entries, num_hashes ntab");
-        std::vector<uint64_t> offs(keys.size() + 1, 0), boff(ntab + 1, 0);
-        std::string data;
-        for (size_t i = 0; i < keys.size(); i++) {
-            data += keys[i];
-            offs[i + 1] = data.size();
-        }
-        data.push_back('\0');
+        std::vector<uint64_t> boff(ntab + 1, 0);
+        detail::PackedKeys pk = detail::pack_keys(keys);
+        pk.data.push_back('\0');
         uint64_t total = 0;
         for (uint32_t nb : num_bits) total += lsmb_serialized_size(nb);
         std::vector<uint8_t> flat(total + 1);
-        check(lsmb_build_batch_blocks(c_, reinterpret_cast<const uint8_t*>(data.data()), offs.data(), 0, keys.size(), ntab,
-                                      seg.data(), num_bits.data(), num_hashes.data(), flat.data(), total, boff.data()));
+        check(lsmb_build_batch_blocks(c_, pk.bytes(), pk.offs.data(), 0, keys.size(), ntab, seg.data(), num_bits.data(),
+                                      num_hashes.data(), flat.data(), total, boff.data()));
         std::vector<std::vector<uint8_t>> blocks(ntab);
         for (size_t t = 0; t < ntab; t++) blocks[t].assign(flat.begin() + boff[t], flat.begin() + boff[t + 1]);
         return blocks;
@@ -153,15 +182,10 @@ class BloomFilter {
             nb[f] = filters[f]->num_bits_;
             kk[f] = filters[f]->num_hashes_;
         }
-        std::vector<uint64_t> offs(keys.size() + 1, 0);
-        std::string data;
-        for (size_t i = 0; i < keys.size(); i++) {
-            data += keys[i];
-            offs[i + 1] = data.size();
-        }
+        const detail::PackedKeys pk = detail::pack_keys(keys);
         std::vector<uint8_t> out(keys.size() * ((nf + 7) / 8));
-        check(lsmb_probe(ctx.get(), w.data(), nb.data(), kk.data(), nf,
-                         reinterpret_cast<const uint8_t*>(data.data()), offs.data(), 0, keys.size(), out.data()));
+        check(lsmb_probe(ctx.get(), w.data(), nb.data(), kk.data(), nf, pk.bytes(), pk.offs.data(), 0, keys.size(),
+                         out.data()));
         return out;
     }
 
@@ -243,14 +267,9 @@ class FilterSet {
     uint64_t live_mask() const { return lsmb_fset_live_mask(fs_); }
 
     std::vector<uint64_t> probe(const std::vector<std::string>& keys) {
-        std::vector<uint64_t> offs(keys.size() + 1, 0);
-        std::string data;
-        for (size_t i = 0; i < keys.size(); i++) {
-            data += keys[i];
-            offs[i + 1] = data.size();
-        }
+        const detail::PackedKeys pk = detail::pack_keys(keys);
         std::vector<uint64_t> out(keys.size());
-        check(lsmb_fset_probe(fs_, u8(data), offs.data(), 0, keys.size(), out.data()));
+        check(lsmb_fset_probe(fs_, pk.bytes(), pk.offs.data(), 0, keys.size(), out.data()));
         return out;
     }
 
@@ -263,17 +282,12 @@ class FilterSet {
         std::vector<uint32_t> index;
     };
     Lists probe_lists(const std::vector<std::string>& keys) {
-        std::vector<uint64_t> offs(keys.size() + 1, 0);
-        std::string data;
-        for (size_t i = 0; i < keys.size(); i++) {
-            data += keys[i];
-            offs[i + 1] = data.size();
-        }
+        const detail::PackedKeys pk = detail::pack_keys(keys);
         Lists out;
         out.index.resize(keys.size());
         for (;;) {
             const uint64_t cap = out.index.size();
-            check(lsmb_fset_probe_lists(fs_, u8(data), offs.data(), 0, keys.size(), out.starts.data(),
+            check(lsmb_fset_probe_lists(fs_, pk.bytes(), pk.offs.data(), 0, keys.size(), out.starts.data(),
                                         out.index.data(), cap));
             out.index.resize(out.starts[64]);
             if (out.starts[64] <= cap) return out;
@@ -347,17 +361,13 @@ class LevelSet {
         if (rows.size() != n || table_ids.size() != n || ranges.size() != n || (crcs && crcs->size() != n))
             throw std::invalid_argument("add_many: rows, table_ids, blocks, ranges and crcs differ in length");
         std::vector<uint8_t> bb, kb;
-        std::vector<uint64_t> boff(n + 1, 0), koff(2 * n + 1, 0);
+        std::vector<uint64_t> boff(n + 1, 0), koff;
         for (size_t t = 0; t < n; t++) {
             bb.insert(bb.end(), blocks[t].begin(), blocks[t].end());
             boff[t + 1] = bb.size();
-            kb.insert(kb.end(), ranges[t].min_key.begin(), ranges[t].min_key.end());
-            koff[2 * t + 1] = kb.size();
-            kb.insert(kb.end(), ranges[t].max_key.begin(), ranges[t].max_key.end());
-            koff[2 * t + 2] = kb.size();
         }
         bb.push_back(0);
-        kb.push_back(0);
+        detail::pack_ranges(ranges, &kb, &koff);
         if (status) status->assign(n, 0);
         check(lsmb_lset_add_batch(ls_, n, rows.data(), table_ids.data(), bb.data(), boff.data(),
                                   crcs ? crcs->data() : nullptr, kb.data(), koff.data(),
@@ -373,16 +383,10 @@ class LevelSet {
         const size_t n = ranges.size();
         if (rows.size() != n || table_ids.size() != n || num_bits.size() != n || num_hashes.size() != n)
             throw std::invalid_argument("add_built: rows, table_ids, num_bits, num_hashes and ranges differ in length");
-        std::vector<uint64_t> woff(n + 1, 0), koff(2 * n + 1, 0);
+        std::vector<uint64_t> woff(n + 1, 0), koff;
         check(lsmb_build_batch_layout(n, num_bits.data(), woff.data()));
         std::vector<uint8_t> kb;
-        for (size_t t = 0; t < n; t++) {
-            kb.insert(kb.end(), ranges[t].min_key.begin(), ranges[t].min_key.end());
-            koff[2 * t + 1] = kb.size();
-            kb.insert(kb.end(), ranges[t].max_key.begin(), ranges[t].max_key.end());
-            koff[2 * t + 2] = kb.size();
-        }
-        kb.push_back(0);
+        detail::pack_ranges(ranges, &kb, &koff);
         check(lsmb_lset_add_batch_dev(ls_, n, rows.data(), table_ids.data(), d_words, woff.data(), num_bits.data(),
                                       num_hashes.data(), kb.data(), koff.data(), stream));
     }
@@ -398,14 +402,9 @@ class LevelSet {
     uint64_t tables(uint32_t row) const { return lsmb_lset_tables(ls_, row); }
 
     std::vector<uint32_t> probe(const std::vector<std::string>& keys) {
-        std::vector<uint64_t> offs(keys.size() + 1, 0);
-        std::string data;
-        for (size_t i = 0; i < keys.size(); i++) {
-            data += keys[i];
-            offs[i + 1] = data.size();
-        }
+        const detail::PackedKeys pk = detail::pack_keys(keys);
         std::vector<uint32_t> out(static_cast<size_t>(rows()) * keys.size());
-        check(lsmb_lset_probe(ls_, u8(data), offs.data(), 0, keys.size(), out.data()));
+        check(lsmb_lset_probe(ls_, pk.bytes(), pk.offs.data(), 0, keys.size(), out.data()));
         return out;
     }
     // Device keys and output (rows() * n uint32_t), asynchronous on `stream`.
@@ -434,16 +433,11 @@ class LevelSet {
         std::vector<uint32_t> ids;   // rows() * keys.size()
     };
     VersionAnswer probe_version(const std::vector<std::string>& keys) {
-        std::vector<uint64_t> offs(keys.size() + 1, 0);
-        std::string data;
-        for (size_t i = 0; i < keys.size(); i++) {
-            data += keys[i];
-            offs[i + 1] = data.size();
-        }
+        const detail::PackedKeys pk = detail::pack_keys(keys);
         VersionAnswer a;
         a.mask.assign(keys.size(), 0);
         a.ids.resize(static_cast<size_t>(rows()) * keys.size());
-        check(lsmb_lset_probe_version(ls_, u8(data), offs.data(), 0, keys.size(), a.mask.data(),
+        check(lsmb_lset_probe_version(ls_, pk.bytes(), pk.offs.data(), 0, keys.size(), a.mask.data(),
                                       a.ids.empty() ? nullptr : a.ids.data()));
         return a;
     }
@@ -477,20 +471,7 @@ class LevelSet {
         std::vector<uint32_t> index;
     };
     Lists probe_lists(const std::vector<std::string>& keys) {
-        std::vector<uint64_t> offs(keys.size() + 1, 0);
-        std::string data;
-        for (size_t i = 0; i < keys.size(); i++) {
-            data += keys[i];
-            offs[i + 1] = data.size();
-        }
-        Lists out;
-        out.starts.assign(total_tables() + 1, 0);
-        check(lsmb_lset_probe_lists(ls_, u8(data), offs.data(), 0, keys.size(), out.starts.data(), nullptr, 0));
-        out.index.resize(out.starts.back());
-        if (!out.index.empty())
-            check(lsmb_lset_probe_lists(ls_, u8(data), offs.data(), 0, keys.size(), out.starts.data(), out.index.data(),
-                                        out.index.size()));
-        return out;
+        return lists_via(lsmb_lset_probe_lists, total_tables(), keys);
     }
     // Device keys, outputs (d_starts: total_tables() + 1 uint64_t, d_index: cap
     // uint32_t) and workspace (lists_work_bytes(n) bytes), asynchronous on `stream`.
@@ -522,20 +503,7 @@ class LevelSet {
     // its row), from one hash per key; starts has version_tables() + 1
     // entries.  A counting call sizes the index.
     Lists probe_version_lists(const std::vector<std::string>& keys) {
-        std::vector<uint64_t> offs(keys.size() + 1, 0);
-        std::string data;
-        for (size_t i = 0; i < keys.size(); i++) {
-            data += keys[i];
-            offs[i + 1] = data.size();
-        }
-        Lists out;
-        out.starts.assign(version_tables() + 1, 0);
-        check(lsmb_lset_probe_version_lists(ls_, u8(data), offs.data(), 0, keys.size(), out.starts.data(), nullptr, 0));
-        out.index.resize(out.starts.back());
-        if (!out.index.empty())
-            check(lsmb_lset_probe_version_lists(ls_, u8(data), offs.data(), 0, keys.size(), out.starts.data(),
-                                                out.index.data(), out.index.size()));
-        return out;
+        return lists_via(lsmb_lset_probe_version_lists, version_tables(), keys);
     }
     // Device keys, outputs (d_starts: version_tables() + 1 uint64_t, d_index:
     // cap uint32_t) and workspace (version_lists_work_bytes(n) bytes),
@@ -551,6 +519,19 @@ class LevelSet {
    private:
     explicit LevelSet(lsmb_lset* h) : ls_(h) {}  // derive
     static const uint8_t* u8(std::string_view s) { return reinterpret_cast<const uint8_t*>(s.data()); }
+    // probe_lists and probe_version_lists: fn the C entry point, total its table count.
+    template <class Fn>
+    Lists lists_via(Fn fn, uint64_t total, const std::vector<std::string>& keys) {
+        const detail::PackedKeys pk = detail::pack_keys(keys);
+        Lists out;
+        out.starts.assign(total + 1, 0);
+        check(fn(ls_, pk.bytes(), pk.offs.data(), 0, keys.size(), out.starts.data(), nullptr, 0));
+        out.index.resize(out.starts.back());
+        if (!out.index.empty())
+            check(fn(ls_, pk.bytes(), pk.offs.data(), 0, keys.size(), out.starts.data(), out.index.data(),
+                     out.index.size()));
+        return out;
+    }
     lsmb_lset* ls_ = nullptr;
 };
 

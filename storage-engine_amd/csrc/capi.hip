@@ -151,6 +151,18 @@ int stage_host_keys(lsmb_ctx* c, const uint8_t* data, const uint64_t* offsets, u
     return LSMB_OK;
 }
 
+int lists_to_host(uint64_t* starts, const uint64_t* d_starts, uint64_t last, uint32_t* index, const uint32_t* d_index,
+                  uint64_t dcap, hipStream_t st) {
+    HIP_TRY(hipMemcpyAsync(starts, d_starts, (last + 1) * 8, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    const uint64_t got = std::min<uint64_t>(starts[last], dcap);
+    if (got) {
+        HIP_TRY(hipMemcpyAsync(index, d_index, got * 4, hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipStreamSynchronize(st));
+    }
+    return LSMB_OK;
+}
+
 // The library's own host build: BloomFilter::insert per key
 // (src/bloom/mod.rs:70-78) with the same xxh3 / exact-modulo code the kernels
 // run, compiled for the host.  Used below host_max_keys(), where a device round

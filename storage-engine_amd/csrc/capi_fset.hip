@@ -377,14 +377,7 @@ int lsmb_fset_probe_lists(lsmb_fset* fs, const uint8_t* data, const uint64_t* of
     HIP_TRY(fs->lstarts.ensure(65 * 8));
     HIP_TRY(fs->lindex.ensure(std::max<uint64_t>(dcap, 1) * 4));
     if (int rc = fset_lists_dev(fs, kb, (uint64_t*)fs->lstarts.p, (uint32_t*)fs->lindex.p, dcap, c->st)) return rc;
-    HIP_TRY(hipMemcpyAsync(starts, fs->lstarts.p, 65 * 8, hipMemcpyDeviceToHost, c->st));
-    HIP_TRY(hipStreamSynchronize(c->st));
-    const uint64_t got = std::min<uint64_t>(starts[64], dcap);
-    if (got) {
-        HIP_TRY(hipMemcpyAsync(index, fs->lindex.p, got * 4, hipMemcpyDeviceToHost, c->st));
-        HIP_TRY(hipStreamSynchronize(c->st));
-    }
-    return LSMB_OK;
+    return lists_to_host(starts, (const uint64_t*)fs->lstarts.p, 64, index, (const uint32_t*)fs->lindex.p, dcap, c->st);
 }
 
 }  // extern "C"

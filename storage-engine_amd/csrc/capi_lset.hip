@@ -2,7 +2,11 @@
 // Host-side plumbing only; the placement of filters in the arena is planned in
 // lset_arena.hpp, a repacking derive in lset_repack.hpp; the kernels are in
 // lset.hip, lset_lists.hip, lset_version.hip, lset_version_lists.hip,
-// lset_repack.hip and crc32.hip.
+// lset_repack.hip and crc32.hip.  Every add stages, copies and commits through
+// lset_stage / lset_commit (a repacking derive through lset_commit_arena); the
+// four lists entry points describe their flavour (LsetListsProbe) and run one
+// device path (lset_lists_dev) or one host path (lset_lists_host, whose
+// copy-back is ctx.hpp's lists_to_host).
 #include <string.h>
 
 #include <algorithm>
@@ -159,17 +163,27 @@ int lset_abandon(lsmb_lset* ls, hipStream_t st, int rc) {
     return rc;
 }
 
-// Step 5, after every copy has completed: the new chunks, the bump state, the
-// tables (tabs[t] into rows[t], its slot from the placement) and the stats.
-void lset_commit(lsmb_lset* ls, const uint32_t* rows, lsmb_lset::Table* tabs, uint64_t ntab, uint64_t up_bytes,
-                 uint64_t up_copies) {
+// Step 5, after every copy has completed.  The arena's half: the set adopts the
+// staged chunks and takes the bump state after the placement.
+void lset_commit_arena(lsmb_lset* ls) {
     LsetStaged& sg = ls->staged;
     for (auto& ch : sg.fresh) ls->chunks.push_back(std::move(ch));
     sg.fresh.clear();
     ls->arena = sg.pl.after;
+}
+
+// Table t of the staged placement has its slot.
+void lset_commit_slot(const lsmb_lset* ls, uint64_t t, lsmb_lset::Table* T) {
+    T->chunk = ls->staged.pl.slot[t].chunk;
+    T->words = (const uint32_t*)ls->staged.words[t];
+}
+
+// All of step 5: the arena, the tables (tabs[t] into rows[t]) and the stats.
+void lset_commit(lsmb_lset* ls, const uint32_t* rows, lsmb_lset::Table* tabs, uint64_t ntab, uint64_t up_bytes,
+                 uint64_t up_copies) {
+    lset_commit_arena(ls);
     for (uint64_t t = 0; t < ntab; t++) {
-        tabs[t].chunk = sg.pl.slot[t].chunk;
-        tabs[t].words = (const uint32_t*)sg.words[t];
+        lset_commit_slot(ls, t, &tabs[t]);
         ls->tables_of(rows[t]).push_back(std::move(tabs[t]));
         if (rows[t] != LSMB_LSET_ROW_L0) ls->nrows = std::max(ls->nrows, rows[t] + 1);
     }
@@ -294,7 +308,8 @@ namespace {
 // The survivors the plan (lset_repack.hpp) moved, already in the child's rows
 // with the parent's addresses: their slots in chunks of the child's own, one
 // k_copy_segs launch on st (NULL: the child's upload stream) and its wait, then
-// the commit.  The items cross through the child's pinned staging.
+// the commit's arena half and the new slots.  The items cross through the
+// child's pinned staging.
 int lset_repack_moved(lsmb_lset* ls, const std::vector<lsmb_lset::Table*>& mv, void* stream, uint64_t* moved_bytes) {
     DevGuard g(ls->c->dev);
     const hipStream_t st = stream ? (hipStream_t)stream : ls->ust;
@@ -322,14 +337,8 @@ int lset_repack_moved(lsmb_lset* ls, const std::vector<lsmb_lset::Table*>& mv, v
         return LSMB_OK;
     };
     if (int rc = copy()) return lset_abandon(ls, st, rc);
-    LsetStaged& sg = ls->staged;
-    for (auto& ch : sg.fresh) ls->chunks.push_back(std::move(ch));
-    sg.fresh.clear();
-    ls->arena = sg.pl.after;  // own_tail: the edit's own add lands in the same chunk
-    for (size_t m = 0; m < mv.size(); m++) {
-        mv[m]->chunk = sg.pl.slot[m].chunk;
-        mv[m]->words = (const uint32_t*)sg.words[m];
-    }
+    lset_commit_arena(ls);  // own_tail: the edit's own add lands in the same chunk
+    for (size_t m = 0; m < mv.size(); m++) lset_commit_slot(ls, m, mv[m]);
     return LSMB_OK;
 }
 
@@ -458,6 +467,17 @@ int lset_batch_check_one(const lsmb_lset* ls, uint64_t ntab, uint64_t l0_before,
     return LSMB_OK;
 }
 
+// What both batches check before any table: the set, then (an empty batch is
+// done) the arrays (`arrays`: none of them null) and the count.
+int lset_batch_check(const lsmb_lset* ls, uint64_t ntab, bool arrays) {
+    if (!ls) return fail(LSMB_EINVAL, "null level set");
+    if (ls->sealed) return fail(LSMB_EINVAL, "level set is sealed: a new Version takes a new set");
+    if (ntab == 0) return LSMB_OK;
+    if (!arrays) return fail(LSMB_EINVAL, "null argument");
+    if (ntab >= UINT32_MAX) return fail(LSMB_EINVAL, "more than 2^32-2 tables in one batch");
+    return LSMB_OK;
+}
+
 // Slots, staging, copies and the CRC check of a batch whose headers passed
 // (nw[t]: table t's u64 words).
 int lset_batch_upload(lsmb_lset* ls, uint64_t ntab, const uint64_t* nw, const uint32_t* ids, const uint8_t* blocks,
@@ -523,11 +543,8 @@ int lset_batch_upload(lsmb_lset* ls, uint64_t ntab, const uint64_t* nw, const ui
 int lsmb_lset_add_batch(lsmb_lset* ls, uint64_t ntab, const uint32_t* rows, const uint32_t* table_ids,
                         const uint8_t* blocks, const uint64_t* block_off, const uint32_t* crcs, const uint8_t* keys,
                         const uint64_t* key_off, int32_t* status) {
-    if (!ls) return fail(LSMB_EINVAL, "null level set");
-    if (ls->sealed) return fail(LSMB_EINVAL, "level set is sealed: a new Version takes a new set");
+    if (int rc = lset_batch_check(ls, ntab, rows && table_ids && block_off && key_off)) return rc;
     if (ntab == 0) return LSMB_OK;
-    if (!rows || !table_ids || !block_off || !key_off) return fail(LSMB_EINVAL, "null argument");
-    if (ntab >= UINT32_MAX) return fail(LSMB_EINVAL, "more than 2^32-2 tables in one batch");
     // every header on the host first: nothing is allocated or uploaded for a batch that fails here
     std::vector<lsmb_lset::Table> tabs(ntab);
     int first_rc = LSMB_OK;
@@ -566,12 +583,9 @@ int lsmb_lset_add_batch(lsmb_lset* ls, uint64_t ntab, const uint32_t* rows, cons
 int lsmb_lset_add_batch_dev(lsmb_lset* ls, uint64_t ntab, const uint32_t* rows, const uint32_t* table_ids,
                             const void* d_words, const uint64_t* word_off, const uint32_t* num_bits,
                             const uint32_t* num_hashes, const uint8_t* keys, const uint64_t* key_off, void* stream) {
-    if (!ls) return fail(LSMB_EINVAL, "null level set");
-    if (ls->sealed) return fail(LSMB_EINVAL, "level set is sealed: a new Version takes a new set");
+    if (int rc = lset_batch_check(ls, ntab, rows && table_ids && d_words && word_off && num_bits && num_hashes && key_off))
+        return rc;
     if (ntab == 0) return LSMB_OK;
-    if (!rows || !table_ids || !d_words || !word_off || !num_bits || !num_hashes || !key_off)
-        return fail(LSMB_EINVAL, "null argument");
-    if (ntab >= UINT32_MAX) return fail(LSMB_EINVAL, "more than 2^32-2 tables in one batch");
     if (reinterpret_cast<uintptr_t>(d_words) & 15) return fail(LSMB_EINVAL, "d_words is not 16-byte aligned");
     // every table on the host first: nothing is allocated or copied for a batch that fails here
     uint64_t at = 0;  // the layout's word_off[t]: the slots back to back, the spans' packed source
@@ -862,70 +876,110 @@ uint64_t lsmb_lset_lists_work_bytes(const lsmb_lset* ls, uint64_t n) {
     return lset_lists_plan(n, ls->nrows, ls->base[ls->nrows]).work_bytes;
 }
 
-// The argument checks shared by both lists entry points; G = all tables.
-static int lset_lists_check(const lsmb_lset* ls, uint64_t n, const void* starts, const void* index, uint64_t cap) {
+// A lists probe over this sealed set, the rows' (lsmb_lset_probe_lists*) or the
+// whole Version's (lsmb_lset_probe_version_lists*): what the two flavours differ
+// in.  A Version without L0 tables is the rows' probe, byte for byte.
+struct LsetListsProbe {
+    uint64_t total = 0;       // tables: the starts have total + 1 entries
+    uint64_t work_bytes = 0;  // the workspace of n keys
+    uint64_t bound = 0;       // no more list entries than this
+    const char* sizer = "";   // the public function that reports work_bytes
+    hipError_t (*launch)(lsmb_lset* ls, const KeyBatch& kb, uint64_t* d_starts, uint32_t* d_index, uint64_t cap,
+                         void* d_work, uint64_t work_bytes, hipStream_t st) = nullptr;
+};
+
+// The argument checks shared by all four lists entry points, then *lp.
+static int lset_lists_desc(const lsmb_lset* ls, bool version, uint64_t n, const void* starts, const void* index,
+                           uint64_t cap, LsetListsProbe* lp) {
     if (int rc = lset_probe_check(ls)) return rc;
     if (n > UINT32_MAX) return fail(LSMB_EINVAL, "more than 2^32-1 keys (the lists hold 32-bit indices)");
-    if (ls->base[ls->nrows] > UINT32_MAX) return fail(LSMB_EINVAL, "more than 2^32-1 tables");
+    const uint64_t G = ls->base[ls->nrows], T0 = version ? ls->l0.size() : 0;
+    if (T0 + G > UINT32_MAX) return fail(LSMB_EINVAL, "more than 2^32-1 tables");
     if (!starts || (cap && !index)) return fail(LSMB_EINVAL, "null output");
+    lp->total = T0 + G;
+    if (T0 == 0) {
+        const LsetListsPlan pl = lset_lists_plan(n, ls->nrows, G);
+        lp->work_bytes = pl.work_bytes;
+        lp->bound = pl.pairs;  // one per row and key
+        lp->sizer = "lsmb_lset_lists_work_bytes";
+        lp->launch = [](lsmb_lset* ls, const KeyBatch& kb, uint64_t* d_starts, uint32_t* d_index, uint64_t cap,
+                        void* d_work, uint64_t work_bytes, hipStream_t st) {
+            return launch_lset_lists(kb, ls->rows, ls->base[ls->nrows], d_starts, d_index, cap, d_work, work_bytes,
+                                     ls->c->num_cus, st);
+        };
+        return LSMB_OK;
+    }
+    const LsetVlistsPlan pl = lset_vlists_plan(n, (uint32_t)T0, ls->nrows, G);
+    lp->work_bytes = pl.work_bytes;
+    lp->bound = pl.entries;  // one per L0 table, row and key
+    lp->sizer = "lsmb_lset_version_lists_work_bytes";
+    lp->launch = [](lsmb_lset* ls, const KeyBatch& kb, uint64_t* d_starts, uint32_t* d_index, uint64_t cap,
+                    void* d_work, uint64_t work_bytes, hipStream_t st) {
+        return launch_lset_version_lists(kb, ls->rows, ls->base[ls->nrows], (const RangedFilter*)ls->l0_desc.p,
+                                         (uint32_t)ls->l0.size(), ls->l0_rg, ls->l0_cl, d_starts, d_index, cap, d_work,
+                                         work_bytes, ls->c->num_cus, st);
+    };
     return LSMB_OK;
+}
+
+// The device entry path.  Nothing to probe (no key, or no table): the starts are cleared on the stream.
+static int lset_lists_dev(lsmb_lset* ls, const LsetListsProbe& lp, const void* d_data, const void* d_offsets,
+                          uint32_t key_len, uint64_t n, void* d_starts, void* d_index, uint64_t cap, void* d_work,
+                          uint64_t work_bytes, void* stream) {
+    const bool idle = n == 0 || lp.total == 0;
+    if (!idle) {
+        if (!d_data) return fail(LSMB_EINVAL, "null keys");
+        if (!d_work || (reinterpret_cast<uintptr_t>(d_work) & 15))
+            return fail(LSMB_EINVAL, "null or misaligned workspace (16-byte alignment)");
+        if (work_bytes < lp.work_bytes)
+            return fail(LSMB_EINVAL, "workspace of %llu bytes, %s asks for %llu", (unsigned long long)work_bytes,
+                        lp.sizer, (unsigned long long)lp.work_bytes);
+    }
+    DevGuard g(ls->c->dev);
+    const hipStream_t st = pick_stream(ls->c, stream);
+    if (idle) {
+        HIP_TRY(hipMemsetAsync(d_starts, 0, (lp.total + 1) * 8, st));
+        return LSMB_OK;
+    }
+    KeyBatch kb{(const uint8_t*)d_data, (const uint64_t*)d_offsets, key_len, n};
+    HIP_TRY(lp.launch(ls, kb, (uint64_t*)d_starts, (uint32_t*)d_index, cap, d_work, work_bytes, st));
+    return LSMB_OK;
+}
+
+// The host entry path, on the context's stream and output scratch.
+static int lset_lists_host(lsmb_lset* ls, const LsetListsProbe& lp, const uint8_t* data, const uint64_t* offsets,
+                           uint32_t key_len, uint64_t n, uint64_t* starts, uint32_t* index, uint64_t cap) {
+    if (n && host_keys_null(data, offsets, key_len, n)) return fail(LSMB_EINVAL, "null keys");
+    memset(starts, 0, (lp.total + 1) * 8);
+    if (n == 0 || lp.total == 0) return LSMB_OK;
+    lsmb_ctx* c = ls->c;
+    DevGuard g(c->dev);
+    // the scratch, carved: workspace | starts | index
+    const uint64_t dcap = std::min<uint64_t>(cap, lp.bound);
+    const uint64_t sbytes = ((lp.total + 1) * 8 + kLlAlign - 1) / kLlAlign * kLlAlign;
+    HIP_TRY(c->out.ensure(lp.work_bytes + sbytes + std::max<uint64_t>(dcap, 1) * 4));
+    uint8_t* w = (uint8_t*)c->out.p;
+    uint64_t* d_starts = (uint64_t*)(w + lp.work_bytes);
+    uint32_t* d_index = (uint32_t*)(w + lp.work_bytes + sbytes);
+    KeyBatch kb;
+    if (int rc = stage_host_keys(c, data, offsets, key_len, n, &kb)) return rc;
+    HIP_TRY(lp.launch(ls, kb, d_starts, d_index, dcap, w, lp.work_bytes, c->st));
+    return lists_to_host(starts, d_starts, lp.total, index, d_index, dcap, c->st);
 }
 
 int lsmb_lset_probe_lists_dev(lsmb_lset* ls, const void* d_data, const void* d_offsets, uint32_t key_len, uint64_t n,
                               void* d_starts, void* d_index, uint64_t cap, void* d_work, uint64_t work_bytes,
                               void* stream) {
-    if (int rc = lset_lists_check(ls, n, d_starts, d_index, cap)) return rc;
-    const uint64_t G = ls->base[ls->nrows];
-    if (n && G) {
-        if (!d_data) return fail(LSMB_EINVAL, "null keys");
-        if (!d_work || (reinterpret_cast<uintptr_t>(d_work) & 15))
-            return fail(LSMB_EINVAL, "null or misaligned workspace (16-byte alignment)");
-        const uint64_t need = lset_lists_plan(n, ls->nrows, G).work_bytes;
-        if (work_bytes < need)
-            return fail(LSMB_EINVAL, "workspace of %llu bytes, lsmb_lset_lists_work_bytes asks for %llu",
-                        (unsigned long long)work_bytes, (unsigned long long)need);
-    }
-    DevGuard g(ls->c->dev);
-    const hipStream_t st = pick_stream(ls->c, stream);
-    if (n == 0 || G == 0) {
-        HIP_TRY(hipMemsetAsync(d_starts, 0, (G + 1) * 8, st));
-        return LSMB_OK;
-    }
-    KeyBatch kb{(const uint8_t*)d_data, (const uint64_t*)d_offsets, key_len, n};
-    HIP_TRY(launch_lset_lists(kb, ls->rows, G, (uint64_t*)d_starts, (uint32_t*)d_index, cap, d_work, work_bytes,
-                              ls->c->num_cus, st));
-    return LSMB_OK;
+    LsetListsProbe lp;
+    if (int rc = lset_lists_desc(ls, false, n, d_starts, d_index, cap, &lp)) return rc;
+    return lset_lists_dev(ls, lp, d_data, d_offsets, key_len, n, d_starts, d_index, cap, d_work, work_bytes, stream);
 }
 
 int lsmb_lset_probe_lists(lsmb_lset* ls, const uint8_t* data, const uint64_t* offsets, uint32_t key_len, uint64_t n,
                           uint64_t* starts, uint32_t* index, uint64_t cap) {
-    if (int rc = lset_lists_check(ls, n, starts, index, cap)) return rc;
-    if (n && host_keys_null(data, offsets, key_len, n)) return fail(LSMB_EINVAL, "null keys");
-    const uint64_t G = ls->base[ls->nrows];
-    memset(starts, 0, (G + 1) * 8);
-    if (n == 0 || G == 0) return LSMB_OK;
-    lsmb_ctx* c = ls->c;
-    DevGuard g(c->dev);
-    // the context's output scratch, carved: workspace | starts | index (no
-    // list entry beyond one per row and key)
-    const LsetListsPlan pl = lset_lists_plan(n, ls->nrows, G);
-    const uint64_t dcap = std::min<uint64_t>(cap, pl.pairs);
-    const uint64_t sbytes = ((G + 1) * 8 + kLlAlign - 1) / kLlAlign * kLlAlign;
-    HIP_TRY(c->out.ensure(pl.work_bytes + sbytes + std::max<uint64_t>(dcap, 1) * 4));
-    uint8_t* w = (uint8_t*)c->out.p;
-    uint64_t* d_starts = (uint64_t*)(w + pl.work_bytes);
-    uint32_t* d_index = (uint32_t*)(w + pl.work_bytes + sbytes);
-    KeyBatch kb;
-    if (int rc = stage_host_keys(c, data, offsets, key_len, n, &kb)) return rc;
-    HIP_TRY(launch_lset_lists(kb, ls->rows, G, d_starts, d_index, dcap, w, pl.work_bytes, c->num_cus, c->st));
-    HIP_TRY(hipMemcpyAsync(starts, d_starts, (G + 1) * 8, hipMemcpyDeviceToHost, c->st));
-    HIP_TRY(hipStreamSynchronize(c->st));
-    const uint64_t got = std::min<uint64_t>(starts[G], dcap);
-    if (got) {
-        HIP_TRY(hipMemcpyAsync(index, d_index, got * 4, hipMemcpyDeviceToHost, c->st));
-        HIP_TRY(hipStreamSynchronize(c->st));
-    }
-    return LSMB_OK;
+    LsetListsProbe lp;
+    if (int rc = lset_lists_desc(ls, false, n, starts, index, cap, &lp)) return rc;
+    return lset_lists_host(ls, lp, data, offsets, key_len, n, starts, index, cap);
 }
 
 // ------------------------------------------------- a whole Version per table
@@ -954,80 +1008,19 @@ uint64_t lsmb_lset_version_lists_work_bytes(const lsmb_lset* ls, uint64_t n) {
     return lset_vlists_plan(n, (uint32_t)ls->l0.size(), ls->nrows, ls->base[ls->nrows]).work_bytes;
 }
 
-// The argument checks shared by both Version lists entry points.
-static int lset_vlists_check(const lsmb_lset* ls, uint64_t n, const void* starts, const void* index, uint64_t cap) {
-    if (int rc = lset_probe_check(ls)) return rc;
-    if (n > UINT32_MAX) return fail(LSMB_EINVAL, "more than 2^32-1 keys (the lists hold 32-bit indices)");
-    if (ls->l0.size() + ls->base[ls->nrows] > UINT32_MAX) return fail(LSMB_EINVAL, "more than 2^32-1 tables");
-    if (!starts || (cap && !index)) return fail(LSMB_EINVAL, "null output");
-    return LSMB_OK;
-}
-
-static int lset_vlists_launch(lsmb_lset* ls, const KeyBatch& kb, uint64_t* d_starts, uint32_t* d_index, uint64_t cap,
-                              void* d_work, uint64_t work_bytes, hipStream_t st) {
-    HIP_TRY(launch_lset_version_lists(kb, ls->rows, ls->base[ls->nrows], (const RangedFilter*)ls->l0_desc.p,
-                                      (uint32_t)ls->l0.size(), ls->l0_rg, ls->l0_cl, d_starts, d_index, cap, d_work,
-                                      work_bytes, ls->c->num_cus, st));
-    return LSMB_OK;
-}
-
 int lsmb_lset_probe_version_lists_dev(lsmb_lset* ls, const void* d_data, const void* d_offsets, uint32_t key_len,
                                       uint64_t n, void* d_starts, void* d_index, uint64_t cap, void* d_work,
                                       uint64_t work_bytes, void* stream) {
-    if (int rc = lset_vlists_check(ls, n, d_starts, d_index, cap)) return rc;
-    if (ls->l0.empty())  // the rows' own lists, byte for byte
-        return lsmb_lset_probe_lists_dev(ls, d_data, d_offsets, key_len, n, d_starts, d_index, cap, d_work, work_bytes,
-                                         stream);
-    const uint64_t V = ls->l0.size() + ls->base[ls->nrows];
-    if (n) {
-        if (!d_data) return fail(LSMB_EINVAL, "null keys");
-        if (!d_work || (reinterpret_cast<uintptr_t>(d_work) & 15))
-            return fail(LSMB_EINVAL, "null or misaligned workspace (16-byte alignment)");
-        const uint64_t need = lsmb_lset_version_lists_work_bytes(ls, n);
-        if (work_bytes < need)
-            return fail(LSMB_EINVAL, "workspace of %llu bytes, lsmb_lset_version_lists_work_bytes asks for %llu",
-                        (unsigned long long)work_bytes, (unsigned long long)need);
-    }
-    DevGuard g(ls->c->dev);
-    const hipStream_t st = pick_stream(ls->c, stream);
-    if (n == 0) {
-        HIP_TRY(hipMemsetAsync(d_starts, 0, (V + 1) * 8, st));
-        return LSMB_OK;
-    }
-    KeyBatch kb{(const uint8_t*)d_data, (const uint64_t*)d_offsets, key_len, n};
-    return lset_vlists_launch(ls, kb, (uint64_t*)d_starts, (uint32_t*)d_index, cap, d_work, work_bytes, st);
+    LsetListsProbe lp;
+    if (int rc = lset_lists_desc(ls, true, n, d_starts, d_index, cap, &lp)) return rc;
+    return lset_lists_dev(ls, lp, d_data, d_offsets, key_len, n, d_starts, d_index, cap, d_work, work_bytes, stream);
 }
 
 int lsmb_lset_probe_version_lists(lsmb_lset* ls, const uint8_t* data, const uint64_t* offsets, uint32_t key_len,
                                   uint64_t n, uint64_t* starts, uint32_t* index, uint64_t cap) {
-    if (int rc = lset_vlists_check(ls, n, starts, index, cap)) return rc;
-    if (ls->l0.empty()) return lsmb_lset_probe_lists(ls, data, offsets, key_len, n, starts, index, cap);
-    if (n && host_keys_null(data, offsets, key_len, n)) return fail(LSMB_EINVAL, "null keys");
-    const uint64_t V = ls->l0.size() + ls->base[ls->nrows];
-    memset(starts, 0, (V + 1) * 8);
-    if (n == 0) return LSMB_OK;
-    lsmb_ctx* c = ls->c;
-    DevGuard g(c->dev);
-    // the context's output scratch, carved: workspace | starts | index (no
-    // list entry beyond one per L0 table, row and key)
-    const LsetVlistsPlan pl = lset_vlists_plan(n, (uint32_t)ls->l0.size(), ls->nrows, ls->base[ls->nrows]);
-    const uint64_t dcap = std::min<uint64_t>(cap, pl.entries);
-    const uint64_t sbytes = ((V + 1) * 8 + kLlAlign - 1) / kLlAlign * kLlAlign;
-    HIP_TRY(c->out.ensure(pl.work_bytes + sbytes + std::max<uint64_t>(dcap, 1) * 4));
-    uint8_t* w = (uint8_t*)c->out.p;
-    uint64_t* d_starts = (uint64_t*)(w + pl.work_bytes);
-    uint32_t* d_index = (uint32_t*)(w + pl.work_bytes + sbytes);
-    KeyBatch kb;
-    if (int rc = stage_host_keys(c, data, offsets, key_len, n, &kb)) return rc;
-    if (int rc = lset_vlists_launch(ls, kb, d_starts, d_index, dcap, w, pl.work_bytes, c->st)) return rc;
-    HIP_TRY(hipMemcpyAsync(starts, d_starts, (V + 1) * 8, hipMemcpyDeviceToHost, c->st));
-    HIP_TRY(hipStreamSynchronize(c->st));
-    const uint64_t got = std::min<uint64_t>(starts[V], dcap);
-    if (got) {
-        HIP_TRY(hipMemcpyAsync(index, d_index, got * 4, hipMemcpyDeviceToHost, c->st));
-        HIP_TRY(hipStreamSynchronize(c->st));
-    }
-    return LSMB_OK;
+    LsetListsProbe lp;
+    if (int rc = lset_lists_desc(ls, true, n, starts, index, cap, &lp)) return rc;
+    return lset_lists_host(ls, lp, data, offsets, key_len, n, starts, index, cap);
 }
 
 }  // extern "C"

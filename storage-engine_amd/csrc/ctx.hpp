@@ -1,7 +1,10 @@
 // ctx.hpp — the per-GPU context behind lsmb_ctx and the host plumbing shared by
 // capi.hip and capi_*.hip (the C ABI, one file per handle), build_dev.hip (build
 // orchestration), stream.hip and multi.hip (one process, several GPUs).  Helpers
-// that cross those files are declared here and defined once, in capi.hip.
+// that cross those files are declared here and defined once, in capi.hip: the
+// error returns, the argument checks, the staging of host keys
+// (stage_host_keys), the copy-back of a lists probe (lists_to_host), the builds
+// and the CRCs.
 // Internal.
 #pragma once
 
@@ -206,6 +209,13 @@ int stage_host_keys(lsmb_ctx* c, const uint8_t* data, const uint64_t* offsets, u
 inline bool host_keys_null(const uint8_t* data, const uint64_t* offsets, uint32_t key_len, uint64_t n) {
     return !data && (offsets ? offsets[n] > offsets[0] : key_len > 0);
 }
+
+// The copy-back of every host lists probe (lsmb_fset_probe_lists,
+// lsmb_lset_probe_lists, lsmb_lset_probe_version_lists), in two steps on st:
+// the last + 1 starts and a wait, then the min(starts[last], dcap) index
+// entries the device wrote and a wait.
+int lists_to_host(uint64_t* starts, const uint64_t* d_starts, uint64_t last, uint32_t* index, const uint32_t* d_index,
+                  uint64_t dcap, hipStream_t st);
 
 // Device build of one batch on `st` into d_words (OR-accumulate; fresh =
 // BloomFilter::new + inserts: d_words is output-only), chunked so the

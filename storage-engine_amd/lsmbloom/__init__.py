@@ -246,6 +246,39 @@ def _key(b):
     return a, len(b)
 
 
+def _host_keys(data, offsets, key_len):
+    """Packed host keys -> (data, n, offsets pointer) as the C ABI takes them:
+    var-length by offsets (n + 1 u64) or fixed-length by key_len (offsets
+    None, a NULL pointer); empty data becomes one zero byte, so that the
+    pointer is never NULL."""
+    data = np.ascontiguousarray(data, dtype=np.uint8).reshape(-1)
+    if offsets is not None:
+        offsets = np.ascontiguousarray(offsets, dtype=np.uint64)
+        n, op = offsets.size - 1, _p(offsets, u64p)
+    else:
+        n, op = (data.size // key_len if key_len else 0), None
+    if data.size == 0:
+        data = np.zeros(1, np.uint8)
+    return data, n, op
+
+
+def _pack_keys(keys):
+    """list of bytes -> (data uint8, offsets uint64[len(keys) + 1])."""
+    lens = np.array([len(k) for k in keys], dtype=np.uint64)
+    offs = np.zeros(len(keys) + 1, dtype=np.uint64)
+    np.cumsum(lens, out=offs[1:])
+    return np.frombuffer(b"".join(bytes(k) for k in keys), dtype=np.uint8), offs
+
+
+def _pack_ranges(ranges):
+    """list of (min_key, max_key) -> (bytes uint8, never empty; offsets
+    uint64[2 * len(ranges) + 1]): table t's bounds at offsets[2t .. 2t + 2]."""
+    flat = [bytes(k) for lo_hi in ranges for k in lo_hi]
+    koff = np.zeros(2 * len(ranges) + 1, dtype=np.uint64)
+    np.cumsum([len(k) for k in flat], out=koff[1:])
+    return np.frombuffer(b"".join(flat) + b"\0", dtype=np.uint8), koff
+
+
 def params(expected_items, false_positive_rate):
     """BloomFilter::new sizing -> (num_bits, num_hashes); ValueError where the reference panics."""
     nb, k = ctypes.c_uint32(), ctypes.c_uint32()
@@ -327,34 +360,18 @@ class Context:
         the keys, src/bloom/mod.rs:102-115) in one call: lsmb_build_block.  Keys are
         fixed-length (key_len) or var-length (offsets, n+1 u64).  `out` may be a
         preallocated uint8 array (e.g. the SST write buffer); returns the array."""
-        data = np.ascontiguousarray(data, dtype=np.uint8).reshape(-1)
-        if offsets is not None:
-            offsets = np.ascontiguousarray(offsets, dtype=np.uint64)
-            n = offsets.size - 1
-            op = _p(offsets, u64p)
-        else:
-            n = data.size // key_len if key_len else 0
-            op = None
+        data, n, op = _host_keys(data, offsets, key_len)
         size = serialized_size(num_bits)
         if out is None:
             out = np.empty(size, dtype=np.uint8)
-        if data.size == 0:
-            data = np.zeros(1, np.uint8)
         _check(lib().lsmb_build_block(self.h, _p(data, u8p), op, key_len, n, num_bits, k, _p(out, u8p), out.size))
         return out
 
     def build_block_crc(self, data, num_bits, k, offsets=None, key_len=0, out=None):
         """build_block + the block's CRC-32 (lsmb_build_block_crc) -> (block, crc)."""
-        data = np.ascontiguousarray(data, dtype=np.uint8).reshape(-1)
-        if offsets is not None:
-            offsets = np.ascontiguousarray(offsets, dtype=np.uint64)
-            n, op = offsets.size - 1, _p(offsets, u64p)
-        else:
-            n, op = (data.size // key_len if key_len else 0), None
+        data, n, op = _host_keys(data, offsets, key_len)
         if out is None:
             out = np.empty(serialized_size(num_bits), dtype=np.uint8)
-        if data.size == 0:
-            data = np.zeros(1, np.uint8)
         crc = ctypes.c_uint32()
         _check(lib().lsmb_build_block_crc(self.h, _p(data, u8p), op, key_len, n, num_bits, k, _p(out, u8p),
                                           out.size, ctypes.byref(crc)))
@@ -388,17 +405,8 @@ class Context:
         arr = (u64p * F)(*[_p(w, u64p) for w in ws])
         nb = np.array([f[1] for f in filters], dtype=np.uint32)
         kk = np.array([f[2] for f in filters], dtype=np.uint32)
-        data = np.ascontiguousarray(data, dtype=np.uint8).reshape(-1)
-        if offsets is not None:
-            offsets = np.ascontiguousarray(offsets, dtype=np.uint64)
-            n = offsets.size - 1
-            op = _p(offsets, u64p)
-        else:
-            n = data.size // key_len if key_len else 0
-            op = None
+        data, n, op = _host_keys(data, offsets, key_len)
         out = np.zeros((n, (F + 7) // 8), dtype=np.uint8)
-        if data.size == 0:
-            data = np.zeros(1, np.uint8)
         _check(lib().lsmb_probe(self.h, arr, _p(nb, u32p), _p(kk, u32p), F, _p(data, u8p), op, key_len, n,
                                 _p(out, u8p)))
         return out
@@ -466,12 +474,7 @@ class Context:
         (blocks, block_off): the tables' serialized bloom blocks back to back
         (uint8) and their ntab + 1 offsets (uint64), the form
         lsmb_lset_add_batch takes.  Runs on the GPU whatever the key count."""
-        data = np.ascontiguousarray(data, dtype=np.uint8).reshape(-1)
-        if offsets is not None:
-            offsets = np.ascontiguousarray(offsets, dtype=np.uint64)
-            n, op = offsets.size - 1, _p(offsets, u64p)
-        else:
-            n, op = (data.size // key_len if key_len else 0), None
+        data, n, op = _host_keys(data, offsets, key_len)
         seg = np.ascontiguousarray(seg, dtype=np.uint64)
         nb = np.ascontiguousarray(num_bits, dtype=np.uint32)
         kk = np.ascontiguousarray(num_hashes, dtype=np.uint32)
@@ -480,8 +483,6 @@ class Context:
             raise ValueError("build_batch_blocks: seg needs ntab + 1 entries, num_hashes ntab")
         boff = np.zeros(ntab + 1, dtype=np.uint64)
         blocks = np.empty(max(sum(serialized_size(int(b)) for b in nb), 1), dtype=np.uint8)
-        if data.size == 0:
-            data = np.zeros(1, np.uint8)
         _check(lib().lsmb_build_batch_blocks(self.h, _p(data, u8p), op, key_len, n, ntab, _p(seg, u64p),
                                              _p(nb, u32p) if ntab else None, _p(kk, u32p) if ntab else None,
                                              _p(blocks, u8p), blocks.size, _p(boff, u64p)))
@@ -696,27 +697,15 @@ class FilterSet:
 
     def probe(self, data, offsets=None, key_len=0):
         """Packed host keys (as Context.probe) -> uint64 mask per key."""
-        data = np.ascontiguousarray(data, dtype=np.uint8).reshape(-1)
-        if offsets is not None:
-            offsets = np.ascontiguousarray(offsets, dtype=np.uint64)
-            n = offsets.size - 1
-            op = _p(offsets, u64p)
-        else:
-            n = data.size // key_len if key_len else 0
-            op = None
+        data, n, op = _host_keys(data, offsets, key_len)
         out = np.zeros(n, dtype=np.uint64)
-        if data.size == 0:
-            data = np.zeros(1, np.uint8)
         _check(lib().lsmb_fset_probe(self.h, _p(data, u8p), op, key_len, n, _p(out if n else np.zeros(1, np.uint64),
                                                                                 u64p)))
         return out
 
     def probe_keys(self, keys):
         """list of bytes -> uint64 mask per key."""
-        lens = np.array([len(k) for k in keys], dtype=np.uint64)
-        offs = np.zeros(len(keys) + 1, dtype=np.uint64)
-        np.cumsum(lens, out=offs[1:])
-        return self.probe(np.frombuffer(b"".join(bytes(k) for k in keys), dtype=np.uint8), offs)
+        return self.probe(*_pack_keys(keys))
 
     def probe_dev(self, data, n, out, offsets=None, key_len=0, stream=None, row_bytes=8):
         """Device keys -> device answer rows: u64 per key (lsmb_fset_probe_dev),
@@ -735,16 +724,7 @@ class FilterSet:
         index[starts[s]:starts[s+1]] = the ascending indices of the keys with
         bit s set in probe()'s mask (lsmb_fset_probe_lists).  cap (default n)
         sizes the first call; a longer answer takes one more with cap = total."""
-        data = np.ascontiguousarray(data, dtype=np.uint8).reshape(-1)
-        if offsets is not None:
-            offsets = np.ascontiguousarray(offsets, dtype=np.uint64)
-            n = offsets.size - 1
-            op = _p(offsets, u64p)
-        else:
-            n = data.size // key_len if key_len else 0
-            op = None
-        if data.size == 0:
-            data = np.zeros(1, np.uint8)
+        data, n, op = _host_keys(data, offsets, key_len)
         starts = np.zeros(65, dtype=np.uint64)
         cap = n if cap is None else int(cap)
         while True:
@@ -758,10 +738,7 @@ class FilterSet:
 
     def probe_lists_keys(self, keys):
         """list of bytes -> (starts, index) as probe_lists."""
-        lens = np.array([len(k) for k in keys], dtype=np.uint64)
-        offs = np.zeros(len(keys) + 1, dtype=np.uint64)
-        np.cumsum(lens, out=offs[1:])
-        return self.probe_lists(np.frombuffer(b"".join(bytes(k) for k in keys), dtype=np.uint8), offs)
+        return self.probe_lists(*_pack_keys(keys))
 
     def probe_lists_dev(self, data, n, starts, index, offsets=None, key_len=0, stream=None):
         """Device keys -> device lists (lsmb_fset_probe_lists_dev): starts an
@@ -880,10 +857,7 @@ class LevelSet:
         boff = np.zeros(n + 1, dtype=np.uint64)
         np.cumsum([len(b) for b in blocks], out=boff[1:])
         bb = np.frombuffer(b"".join(bytes(b) for b in blocks) + b"\0", dtype=np.uint8)
-        flat = [bytes(k) for lo_hi in ranges for k in lo_hi]
-        koff = np.zeros(2 * n + 1, dtype=np.uint64)
-        np.cumsum([len(k) for k in flat], out=koff[1:])
-        kb = np.frombuffer(b"".join(flat) + b"\0", dtype=np.uint8)
+        kb, koff = _pack_ranges(ranges)
         cc = None if crcs is None else np.ascontiguousarray(crcs, dtype=np.uint32)
         status = np.zeros(max(n, 1), dtype=np.int32)
         rc = lib().lsmb_lset_add_batch(self.h, n, _p(rows, u32p) if n else None, _p(ids, u32p) if n else None,
@@ -913,10 +887,7 @@ class LevelSet:
         woff = build_batch_layout(nb)
         if words.numel() * words.element_size() < 8 * int(woff[n]):
             raise ValueError("add_built: words is smaller than the layout of num_bits")
-        flat = [bytes(k) for lo_hi in ranges for k in lo_hi]
-        koff = np.zeros(2 * n + 1, dtype=np.uint64)
-        np.cumsum([len(k) for k in flat], out=koff[1:])
-        kb = np.frombuffer(b"".join(flat) + b"\0", dtype=np.uint8)
+        kb, koff = _pack_ranges(ranges)
         _check(lib().lsmb_lset_add_batch_dev(self.h, n, _p(rows, u32p) if n else None, _p(ids, u32p) if n else None,
                                              vp(words.data_ptr()), _p(woff, u64p), _p(nb, u32p) if n else None,
                                              _p(kk, u32p) if n else None, _p(kb, u8p), _p(koff, u64p),
@@ -942,27 +913,15 @@ class LevelSet:
 
     def probe(self, data, offsets=None, key_len=0):
         """Packed host keys (as Context.probe) -> uint32 table ids, shape (rows(), n)."""
-        data = np.ascontiguousarray(data, dtype=np.uint8).reshape(-1)
-        if offsets is not None:
-            offsets = np.ascontiguousarray(offsets, dtype=np.uint64)
-            n = offsets.size - 1
-            op = _p(offsets, u64p)
-        else:
-            n = data.size // key_len if key_len else 0
-            op = None
+        data, n, op = _host_keys(data, offsets, key_len)
         out = np.empty((self.rows(), n), dtype=np.uint32)
-        if data.size == 0:
-            data = np.zeros(1, np.uint8)
         _check(lib().lsmb_lset_probe(self.h, _p(data, u8p), op, key_len, n,
                                      _p(out if out.size else np.zeros(1, np.uint32), u32p)))
         return out
 
     def probe_keys(self, keys):
         """list of bytes -> uint32 table ids, shape (rows(), len(keys))."""
-        lens = np.array([len(k) for k in keys], dtype=np.uint64)
-        offs = np.zeros(len(keys) + 1, dtype=np.uint64)
-        np.cumsum(lens, out=offs[1:])
-        return self.probe(np.frombuffer(b"".join(bytes(k) for k in keys), dtype=np.uint8), offs)
+        return self.probe(*_pack_keys(keys))
 
     def probe_dev(self, data, n, out, offsets=None, key_len=0, stream=None):
         """Device keys -> device table ids (lsmb_lset_probe_dev): out an int32 /
@@ -988,18 +947,9 @@ class LevelSet:
         min_j <= key_i <= max_j and may_contain(filter j, key_i) for the L0
         table at position j (a reader visits set bits from the highest down),
         ids exactly probe()'s."""
-        data = np.ascontiguousarray(data, dtype=np.uint8).reshape(-1)
-        if offsets is not None:
-            offsets = np.ascontiguousarray(offsets, dtype=np.uint64)
-            n = offsets.size - 1
-            op = _p(offsets, u64p)
-        else:
-            n = data.size // key_len if key_len else 0
-            op = None
+        data, n, op = _host_keys(data, offsets, key_len)
         mask = np.zeros(n, dtype=np.uint64)
         out = np.empty((self.rows(), n), dtype=np.uint32)
-        if data.size == 0:
-            data = np.zeros(1, np.uint8)
         _check(lib().lsmb_lset_probe_version(self.h, _p(data, u8p), op, key_len, n,
                                              _p(mask if n else np.zeros(1, np.uint64), u64p),
                                              _p(out, u32p) if out.size else None))
@@ -1007,10 +957,7 @@ class LevelSet:
 
     def probe_version_keys(self, keys):
         """list of bytes -> (mask, ids) as probe_version."""
-        lens = np.array([len(k) for k in keys], dtype=np.uint64)
-        offs = np.zeros(len(keys) + 1, dtype=np.uint64)
-        np.cumsum(lens, out=offs[1:])
-        return self.probe_version(np.frombuffer(b"".join(bytes(k) for k in keys), dtype=np.uint8), offs)
+        return self.probe_version(*_pack_keys(keys))
 
     def probe_version_dev(self, data, n, mask, out, offsets=None, key_len=0, stream=None):
         """Device keys -> device answers (lsmb_lset_probe_version_dev): mask an
@@ -1034,6 +981,29 @@ class LevelSet:
         _check(lib().lsmb_lset_table_order(self.h, _p(ids, u32p), _p(base, u64p)))
         return ids[:self.total_tables()], base
 
+    def _lists(self, fn, total, data, offsets, key_len, cap):
+        """probe_lists and probe_version_lists: fn the C entry point, total its table count."""
+        data, n, op = _host_keys(data, offsets, key_len)
+        starts = np.zeros(total + 1, dtype=np.uint64)
+        if cap is None:
+            _check(fn(self.h, _p(data, u8p), op, key_len, n, _p(starts, u64p), None, 0))
+            cap = int(starts[-1])
+            if cap == 0:
+                return starts, np.zeros(0, dtype=np.uint32)
+        cap = int(cap)
+        index = np.empty(max(cap, 1), dtype=np.uint32)
+        _check(fn(self.h, _p(data, u8p), op, key_len, n, _p(starts, u64p), _p(index, u32p) if cap else None, cap))
+        return starts, index[:min(int(starts[-1]), cap)]
+
+    def _lists_dev(self, fn, data, n, starts, index, work, offsets, key_len, stream):
+        """probe_lists_dev and probe_version_lists_dev: fn the C entry point."""
+        offs = vp(offsets.data_ptr()) if offsets is not None else None
+        cap = int(index.numel()) if index is not None else 0
+        wb = int(work.numel() * work.element_size()) if work is not None else 0
+        _check(fn(self.h, vp(data.data_ptr()), offs, key_len, n, vp(starts.data_ptr()),
+                  vp(index.data_ptr()) if cap else None, cap, vp(work.data_ptr()) if wb else None, wb,
+                  Context._stream(stream)))
+
     def lists_work_bytes(self, n):
         """Bytes of device workspace probe_lists_dev needs for n keys."""
         return int(lib().lsmb_lset_lists_work_bytes(self.h, int(n)))
@@ -1044,34 +1014,11 @@ class LevelSet:
         indices of the keys for which probe() answers the table of ordinal g
         (table_order()) in g's row (lsmb_lset_probe_lists).  cap=None sizes
         index from a counting call."""
-        data = np.ascontiguousarray(data, dtype=np.uint8).reshape(-1)
-        if offsets is not None:
-            offsets = np.ascontiguousarray(offsets, dtype=np.uint64)
-            n = offsets.size - 1
-            op = _p(offsets, u64p)
-        else:
-            n = data.size // key_len if key_len else 0
-            op = None
-        if data.size == 0:
-            data = np.zeros(1, np.uint8)
-        starts = np.zeros(self.total_tables() + 1, dtype=np.uint64)
-        if cap is None:
-            _check(lib().lsmb_lset_probe_lists(self.h, _p(data, u8p), op, key_len, n, _p(starts, u64p), None, 0))
-            cap = int(starts[-1])
-            if cap == 0:
-                return starts, np.zeros(0, dtype=np.uint32)
-        cap = int(cap)
-        index = np.empty(max(cap, 1), dtype=np.uint32)
-        _check(lib().lsmb_lset_probe_lists(self.h, _p(data, u8p), op, key_len, n, _p(starts, u64p),
-                                           _p(index, u32p) if cap else None, cap))
-        return starts, index[:min(int(starts[-1]), cap)]
+        return self._lists(lib().lsmb_lset_probe_lists, self.total_tables(), data, offsets, key_len, cap)
 
     def probe_lists_keys(self, keys):
         """list of bytes -> (starts, index) as probe_lists."""
-        lens = np.array([len(k) for k in keys], dtype=np.uint64)
-        offs = np.zeros(len(keys) + 1, dtype=np.uint64)
-        np.cumsum(lens, out=offs[1:])
-        return self.probe_lists(np.frombuffer(b"".join(bytes(k) for k in keys), dtype=np.uint8), offs)
+        return self.probe_lists(*_pack_keys(keys))
 
     def probe_lists_dev(self, data, n, starts, index, work, offsets=None, key_len=0, stream=None):
         """Device keys -> device lists (lsmb_lset_probe_lists_dev): starts an
@@ -1080,12 +1027,7 @@ class LevelSet:
         uint8 tensor of at least lists_work_bytes(n) bytes — the probe's only
         scratch, so probes on different streams take different tensors.  starts
         is always exact; entries at and past the capacity are not written."""
-        offs = vp(offsets.data_ptr()) if offsets is not None else None
-        cap = int(index.numel()) if index is not None else 0
-        wb = int(work.numel() * work.element_size()) if work is not None else 0
-        _check(lib().lsmb_lset_probe_lists_dev(self.h, vp(data.data_ptr()), offs, key_len, n, vp(starts.data_ptr()),
-                                               vp(index.data_ptr()) if cap else None, cap,
-                                               vp(work.data_ptr()) if wb else None, wb, Context._stream(stream)))
+        self._lists_dev(lib().lsmb_lset_probe_lists_dev, data, n, starts, index, work, offsets, key_len, stream)
 
     def version_tables(self):
         """L0 tables + tables of all rows (0 before seal): the Version lists'
@@ -1112,34 +1054,11 @@ class LevelSet:
         probe() answers the row table of ordinal v - l0_tables(), from one
         hash per key (lsmb_lset_probe_version_lists).  cap=None sizes index
         from a counting call."""
-        data = np.ascontiguousarray(data, dtype=np.uint8).reshape(-1)
-        if offsets is not None:
-            offsets = np.ascontiguousarray(offsets, dtype=np.uint64)
-            n = offsets.size - 1
-            op = _p(offsets, u64p)
-        else:
-            n = data.size // key_len if key_len else 0
-            op = None
-        if data.size == 0:
-            data = np.zeros(1, np.uint8)
-        starts = np.zeros(self.version_tables() + 1, dtype=np.uint64)
-        if cap is None:
-            _check(lib().lsmb_lset_probe_version_lists(self.h, _p(data, u8p), op, key_len, n, _p(starts, u64p), None, 0))
-            cap = int(starts[-1])
-            if cap == 0:
-                return starts, np.zeros(0, dtype=np.uint32)
-        cap = int(cap)
-        index = np.empty(max(cap, 1), dtype=np.uint32)
-        _check(lib().lsmb_lset_probe_version_lists(self.h, _p(data, u8p), op, key_len, n, _p(starts, u64p),
-                                                   _p(index, u32p) if cap else None, cap))
-        return starts, index[:min(int(starts[-1]), cap)]
+        return self._lists(lib().lsmb_lset_probe_version_lists, self.version_tables(), data, offsets, key_len, cap)
 
     def probe_version_lists_keys(self, keys):
         """list of bytes -> (starts, index) as probe_version_lists."""
-        lens = np.array([len(k) for k in keys], dtype=np.uint64)
-        offs = np.zeros(len(keys) + 1, dtype=np.uint64)
-        np.cumsum(lens, out=offs[1:])
-        return self.probe_version_lists(np.frombuffer(b"".join(bytes(k) for k in keys), dtype=np.uint8), offs)
+        return self.probe_version_lists(*_pack_keys(keys))
 
     def probe_version_lists_dev(self, data, n, starts, index, work, offsets=None, key_len=0, stream=None):
         """Device keys -> device lists (lsmb_lset_probe_version_lists_dev):
@@ -1149,13 +1068,8 @@ class LevelSet:
         probe's only scratch, so probes on different streams take different
         tensors.  starts is always exact; entries at and past the capacity are
         not written."""
-        offs = vp(offsets.data_ptr()) if offsets is not None else None
-        cap = int(index.numel()) if index is not None else 0
-        wb = int(work.numel() * work.element_size()) if work is not None else 0
-        _check(lib().lsmb_lset_probe_version_lists_dev(self.h, vp(data.data_ptr()), offs, key_len, n,
-                                                       vp(starts.data_ptr()), vp(index.data_ptr()) if cap else None, cap,
-                                                       vp(work.data_ptr()) if wb else None, wb,
-                                                       Context._stream(stream)))
+        self._lists_dev(lib().lsmb_lset_probe_version_lists_dev, data, n, starts, index, work, offsets, key_len,
+                        stream)
 
 
 def build_strategy(num_bits, n, k=7):
@@ -1250,16 +1164,9 @@ class Multi:
         _check(lib().lsmb_multi_build_fixed_dev(self.h, karr, _p(n, u64p), key_len, num_bits, k, warr))
 
     def build_block(self, data, num_bits, k, offsets=None, key_len=0, out=None):
-        data = np.ascontiguousarray(data, dtype=np.uint8).reshape(-1)
-        if offsets is not None:
-            offsets = np.ascontiguousarray(offsets, dtype=np.uint64)
-            n, op = offsets.size - 1, _p(offsets, u64p)
-        else:
-            n, op = (data.size // key_len if key_len else 0), None
+        data, n, op = _host_keys(data, offsets, key_len)
         if out is None:
             out = np.empty(serialized_size(num_bits), dtype=np.uint8)
-        if data.size == 0:
-            data = np.zeros(1, np.uint8)
         _check(lib().lsmb_multi_build_block(self.h, _p(data, u8p), op, key_len, n, num_bits, k, _p(out, u8p),
                                             out.size))
         return out

@@ -22,6 +22,7 @@ import pytest
 import keygen
 import lsmbloom
 from lsmbloom import LevelSet, u8p, u32p, u64p
+from lset_support import cpp_bin
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 EINVAL = lsmbloom.LSMB_EINVAL
@@ -163,18 +164,10 @@ def test_batched_build_needs_a_device():
     assert not out.any()
 
 
-CPP_BIN = os.path.join(ROOT, "storage-engine_amd", "build", "build_batch_test")
-
-
-def _cpp_bin():
-    if not os.path.exists(CPP_BIN):
-        subprocess.run(["make", "-s", "-C", os.path.join(ROOT, "storage-engine_amd"), "build/build_batch_test"],
-                       check=True)
-    return CPP_BIN
 
 
 def test_cpp_mirror_build_batch_argument_checks():
-    r = subprocess.run([_cpp_bin()], capture_output=True, text=True, timeout=300)
+    r = subprocess.run([cpp_bin("build_batch_test")], capture_output=True, text=True, timeout=300)
     assert r.returncode == 0, r.stdout + r.stderr
 
 
@@ -509,6 +502,6 @@ def test_built_words_go_into_a_level_set_device_to_device(oracle):
 
 @pytest.mark.gpu
 def test_cpp_mirror_build_batch_gpu():
-    r = subprocess.run([_cpp_bin(), "--gpu"], capture_output=True, text=True, timeout=300)
+    r = subprocess.run([cpp_bin("build_batch_test"), "--gpu"], capture_output=True, text=True, timeout=300)
     assert r.returncode == 0, r.stdout + r.stderr
     assert "FAIL" not in r.stdout

@@ -324,3 +324,31 @@ def test_missing_library_fails_loudly(tmp_path):
     r = subprocess.run([sys.executable, "-c", code], env=env, capture_output=True, text=True, timeout=300)
     assert r.returncode == 3, (r.returncode, r.stdout, r.stderr)
     assert "not built" in r.stdout
+
+
+def test_key_and_range_packing_helpers_at_their_edges():
+    """What every host probe and batch add hands the C ABI (lsmbloom._host_keys,
+    _pack_keys, _pack_ranges): the key count, the offsets behind the pointer
+    (None: fixed-length keys) and the one zero byte that stands in for no data."""
+    def form(data, offsets, key_len):
+        d, n, op = lsmbloom._host_keys(data, offsets, key_len)
+        assert d.dtype == np.uint8 and d.ndim == 1 and d.flags.c_contiguous
+        return d.tolist(), n, None if op is None else op[:n + 1]
+
+    abcdef = np.frombuffer(b"abcdef", np.uint8)
+    assert form(*lsmbloom._pack_keys([]), 0) == ([0], 0, [0])                  # no keys
+    assert form(*lsmbloom._pack_keys([b""]), 0) == ([0], 1, [0, 0])            # one empty key
+    assert form(np.zeros(0, np.uint8), None, 0) == ([0], 0, None)              # key_len = 0, empty data
+    assert form(np.zeros(0, np.uint8), None, 16) == ([0], 0, None)
+    assert form(abcdef, None, 3) == (list(b"abcdef"), 2, None)                 # the same bytes, both forms
+    assert form(*lsmbloom._pack_keys([b"abc", b"def"]), 0) == (list(b"abcdef"), 2, [0, 3, 6])
+    assert form(abcdef.reshape(2, 3), [0, 1, 6], 0) == (list(b"abcdef"), 2, [0, 1, 6])
+    assert form(abcdef, None, 4) == (list(b"abcdef"), 1, None)                 # a partial last key is not a key
+    data, offs = lsmbloom._pack_keys([b"a", b"", bytearray(b"bc")])
+    assert data.dtype == np.uint8 and data.tobytes() == b"abc"
+    assert offs.dtype == np.uint64 and offs.tolist() == [0, 1, 1, 3]
+    kb, koff = lsmbloom._pack_ranges([(b"", b"ab"), (b"c", b"")])              # an empty min, an empty max
+    assert kb.dtype == np.uint8 and kb.tobytes() == b"abc\0"
+    assert koff.dtype == np.uint64 and koff.tolist() == [0, 0, 2, 3, 3]
+    kb, koff = lsmbloom._pack_ranges([])
+    assert kb.tobytes() == b"\0" and koff.tolist() == [0]

@@ -15,18 +15,7 @@ import pytest
 import keygen
 import lsmbloom
 from lsmbloom import BloomFilter, FilterSet
-
-
-def expected_masks(oracle, tables, keys):
-    """tables: {slot: (words, num_bits, k, lo, hi)} -> list of uint64 masks."""
-    data, offs = keygen.pack(keys)
-    out = [0] * len(keys)
-    for s, (w, nb, k, lo, hi) in tables.items():
-        hit = oracle.probe([(w, nb, k)], data, offsets=offs)[:, 0]
-        for i, key in enumerate(keys):
-            if hit[i] and lo <= key <= hi:
-                out[i] |= 1 << s
-    return out
+from lset_support import expected_masks
 
 
 def sst_tables(oracle, ntab, per, seed):

@@ -9,52 +9,23 @@ ordering (expected_masks, as tests/test_fset.py) through lists_from_masks;
 every GPU test also holds the lists against the set's own mask probe.
 """
 import ctypes
-import os
 import subprocess
 
 import numpy as np
 import pytest
 
 import keygen
+import lset_support
 import lsmbloom
 from lsmbloom import BloomFilter, FilterSet
+from lset_support import check_mask_lists as check_lists, cpp_bin, lists_from_masks
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CPP_BIN = os.path.join(ROOT, "storage-engine_amd", "build", "fset_lists_test")
 vp = ctypes.c_void_p
 
 
 def expected_masks(oracle, tables, keys):
     """tables: {slot: (words, num_bits, k, lo, hi)} -> uint64 mask per key."""
-    data, offs = keygen.pack(keys)
-    out = [0] * len(keys)
-    for s, (w, nb, k, lo, hi) in tables.items():
-        hit = oracle.probe([(w, nb, k)], data, offsets=offs)[:, 0]
-        for i, key in enumerate(keys):
-            if hit[i] and lo <= key <= hi:
-                out[i] |= 1 << s
-    return np.array(out, dtype=np.uint64)
-
-
-def lists_from_masks(masks):
-    """uint64 mask per key -> (starts uint64[65], index uint32[total])."""
-    masks = np.asarray(masks, dtype=np.uint64)
-    starts = np.zeros(65, dtype=np.uint64)
-    runs = []
-    for s in range(64):
-        idx = np.nonzero((masks >> np.uint64(s)) & np.uint64(1))[0].astype(np.uint32)
-        runs.append(idx)
-        starts[s + 1] = starts[s] + np.uint64(idx.size)
-    return starts, (np.concatenate(runs) if runs else np.zeros(0, np.uint32))
-
-
-def check_lists(got, masks, what=""):
-    starts, index = got
-    es, ei = lists_from_masks(masks)
-    assert starts.dtype == np.uint64 and starts.shape == (65,), what
-    assert index.dtype == np.uint32, what
-    assert np.array_equal(starts, es), (what, starts, es)
-    assert np.array_equal(index, ei), what
+    return np.array(lset_support.expected_masks(oracle, tables, keys), dtype=np.uint64)
 
 
 def sst_tables(oracle, ntab, per, seed):
@@ -109,15 +80,8 @@ def test_lists_from_masks_on_a_hand_written_example():
 
 
 def test_cpp_mirror_lists_argument_checks():
-    r = subprocess.run([_cpp_bin()], capture_output=True, text=True, timeout=300)
+    r = subprocess.run([cpp_bin("fset_lists_test")], capture_output=True, text=True, timeout=300)
     assert r.returncode == 0, r.stdout + r.stderr
-
-
-def _cpp_bin():
-    if not os.path.exists(CPP_BIN):
-        subprocess.run(["make", "-s", "-C", os.path.join(ROOT, "storage-engine_amd"), "build/fset_lists_test"],
-                       check=True)
-    return CPP_BIN
 
 
 # ------------------------------------------------------------------- on the GPU
@@ -423,6 +387,6 @@ def test_lists_empty_set_and_no_keys():
 
 @pytest.mark.gpu
 def test_cpp_mirror_lists_gpu():
-    r = subprocess.run([_cpp_bin(), "--gpu"], capture_output=True, text=True, timeout=300)
+    r = subprocess.run([cpp_bin("fset_lists_test"), "--gpu"], capture_output=True, text=True, timeout=300)
     assert r.returncode == 0, r.stdout + r.stderr
     assert "FAIL" not in r.stdout

@@ -25,6 +25,7 @@ import pytest
 import keygen
 import lsmbloom
 from lsmbloom import BloomFilter, FilterSet
+from lset_support import check_mask_lists as check_lists, expected_masks
 
 pytestmark = pytest.mark.gpu
 
@@ -431,8 +432,6 @@ def test_filter_set_with_a_wide_filter(ctx, oracle):
     SST-sized new(1000, .01) one, each with a key range: mask rows = the
     oracle's bloom answer AND the range check (tests/test_fset.py's
     computation), and probe_lists is their transpose."""
-    from test_fset import expected_masks
-    from test_fset_lists import check_lists
     k = 7
     fs = FilterSet(ctx)
     big = _keys("K8")

@@ -11,7 +11,6 @@ bytes ordering (the same lexicographic order as Rust's [u8]) and bisect over
 each row's sorted ranges; never from the library.  Every comparison is exact
 equality over all rows() * n answers.
 """
-import bisect
 import ctypes
 import os
 import subprocess
@@ -22,49 +21,11 @@ import pytest
 import keygen
 import lsmbloom
 from lsmbloom import BloomFilter, FilterSet, LevelSet
+from lset_support import SIZINGS, add_tables, build_table, cpp_bin, expected_ids
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CPP_BIN = os.path.join(ROOT, "storage-engine_amd", "build", "lset_test")
 NONE = lsmbloom.LSMB_LSET_NONE
 vp = ctypes.c_void_p
-
-
-def expected_ids(oracle, rows, keys):
-    """rows: per row, a list of (table_id, words, num_bits, k, lo, hi) with
-    disjoint [lo, hi] -> uint32 [len(rows), len(keys)]."""
-    out = np.full((len(rows), len(keys)), NONE, dtype=np.uint32)
-    for r, tabs in enumerate(rows):
-        tabs = sorted(tabs, key=lambda t: t[4])
-        los = [t[4] for t in tabs]
-        for a, b in zip(tabs, tabs[1:]):
-            assert a[4] <= a[5] < b[4], "the test's own tables overlap"
-        for i, key in enumerate(keys):
-            j = bisect.bisect_right(los, key) - 1  # the last table whose min_key <= key
-            if j < 0:
-                continue
-            tid, w, nb, k, _lo, hi = tabs[j]
-            if key <= hi and oracle.may_contain(w, nb, k, key):
-                out[r, i] = tid
-    return out
-
-
-def build_table(oracle, tid, keys, sizing, k=None):
-    """(table_id, words, num_bits, k, min_key, max_key) of sorted `keys`, the
-    filter sized by lsmbloom.params(*sizing); k overrides num_hashes."""
-    nb, kk = lsmbloom.params(*sizing)
-    data, offs = keygen.pack(keys)
-    w = oracle.build_var(data, offs, nb, kk if k is None else k)
-    return (tid, w, nb, kk if k is None else k, keys[0], keys[-1])
-
-
-def add_tables(ls, oracle, row, tabs):
-    """Adds a row's tables: most from the serialized block, every third and
-    each k = 0 one from the filter words."""
-    for tid, w, nb, k, lo, hi in tabs:
-        if k == 0 or tid % 3 == 0:
-            ls.add_filter(row, tid, BloomFilter(w, k, nb), lo, hi)
-        else:
-            ls.add(row, tid, oracle.serialize(w, nb, k), lo, hi)
 
 
 # ---------------------------------------------------------------- without a GPU
@@ -107,21 +68,12 @@ def test_lset_row_order_and_search_host(tmp_path):
     assert "all passed" in r.stdout
 
 
-def _cpp_bin():
-    if not os.path.exists(CPP_BIN):
-        subprocess.run(["make", "-s", "-C", os.path.join(ROOT, "storage-engine_amd"), "build/lset_test"], check=True)
-    return CPP_BIN
-
-
 def test_cpp_mirror_level_set_argument_checks():
-    r = subprocess.run([_cpp_bin()], capture_output=True, text=True, timeout=300)
+    r = subprocess.run([cpp_bin("lset_test")], capture_output=True, text=True, timeout=300)
     assert r.returncode == 0, r.stdout + r.stderr
 
 
 # ------------------------------------------------------------------- on the GPU
-
-SIZINGS = [(40, 0.01), (1000, 0.01), (40000, 0.01), (40, 1e-4)]  # SST-small, < 2^14 bits, > 2^14 bits, k > 8
-
 
 @pytest.mark.gpu
 def test_lset_three_rows_match_range_and_bloom_checks(oracle):
@@ -364,6 +316,6 @@ def test_lset_agrees_with_a_filter_set_of_64_tables(oracle):
 
 @pytest.mark.gpu
 def test_cpp_mirror_level_set_gpu():
-    r = subprocess.run([_cpp_bin(), "--gpu"], capture_output=True, text=True, timeout=300)
+    r = subprocess.run([cpp_bin("lset_test"), "--gpu"], capture_output=True, text=True, timeout=300)
     assert r.returncode == 0, r.stdout + r.stderr
     assert "FAIL" not in r.stdout

@@ -22,55 +22,19 @@ import pytest
 
 import keygen
 import lsmbloom
-from lsmbloom import BloomFilter, LevelSet
-from test_lset import add_tables, build_table, expected_ids
+from lsmbloom import LevelSet
+from lset_support import (POISON, add_tables, always_maybe, build_table, check_lists, cpp_bin, dev_lists, expected_ids,
+                          lists_from_ids)
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CPP_BIN = os.path.join(ROOT, "storage-engine_amd", "build", "lset_lists_test")
 PLAN_SRC = os.path.join(ROOT, "tests", "cpp", "lset_lists_plan_test.cpp")
 NONE = lsmbloom.LSMB_LSET_NONE
-POISON = 0xDEADBEEF
 vp = ctypes.c_void_p
-
-
-def lists_from_ids(ids_rn, order_ids):
-    """probe()'s uint32 [R, n] table ids + table_order()'s ids (unique) ->
-    (starts uint64[G + 1], index uint32[total])."""
-    order_ids = np.asarray(order_ids, dtype=np.uint32)
-    G = order_ids.size
-    assert np.unique(order_ids).size == G, "the expectation needs unique table ids"
-    R, n = ids_rn.shape
-    flat = ids_rn.reshape(-1)                      # (row, key) order
-    hit = flat != NONE
-    sorter = np.argsort(order_ids, kind="stable")
-    if G:
-        pos = np.searchsorted(order_ids[sorter], flat[hit])
-        assert (order_ids[sorter][pos] == flat[hit]).all()
-        ordinal = sorter[pos]
-    else:
-        assert not hit.any()
-        ordinal = np.zeros(0, np.int64)
-    key_idx = np.tile(np.arange(n, dtype=np.uint32), R)[hit]
-    by_table = np.argsort(ordinal, kind="stable")
-    starts = np.searchsorted(ordinal[by_table], np.arange(G + 1), side="left").astype(np.uint64)
-    return starts, key_idx[by_table]
 
 
 def lists_from_ordinals(ord_rn, G):
     """uint32 [R, n] ordinals (NONE: no table) -> (starts, index)."""
     return lists_from_ids(ord_rn, np.arange(G, dtype=np.uint32))
-
-
-def check_lists(got, exp, what=""):
-    starts, index = got
-    es, ei = exp
-    assert starts.dtype == np.uint64 and starts.shape == es.shape, what
-    assert index.dtype == np.uint32, what
-    assert np.array_equal(starts, es), (what, np.argwhere(starts != es)[:10])
-    assert index.shape == ei.shape and np.array_equal(index, ei), (what, index[:20], ei[:20])
-    for g in np.nonzero(np.diff(es.astype(np.int64)) > 1)[0][:50]:  # (implied by equality; states the contract)
-        run = index[int(es[g]):int(es[g + 1])]
-        assert (np.diff(run.astype(np.int64)) > 0).all(), (what, g)
 
 
 # ---------------------------------------------------------------- without a GPU
@@ -130,15 +94,8 @@ def test_lset_lists_plan_and_reference_host(tmp_path, flags):
     assert "all passed" in r.stdout
 
 
-def _cpp_bin():
-    if not os.path.exists(CPP_BIN):
-        subprocess.run(["make", "-s", "-C", os.path.join(ROOT, "storage-engine_amd"), "build/lset_lists_test"],
-                       check=True)
-    return CPP_BIN
-
-
 def test_cpp_mirror_level_set_lists_argument_checks():
-    r = subprocess.run([_cpp_bin()], capture_output=True, text=True, timeout=300)
+    r = subprocess.run([cpp_bin("lset_lists_test")], capture_output=True, text=True, timeout=300)
     assert r.returncode == 0, r.stdout + r.stderr
 
 
@@ -149,37 +106,6 @@ def ctx():
     c = lsmbloom.Context(0)
     yield c
     c.close()
-
-
-def always_maybe():
-    """A 64-bit filter with no hash: may_contain is always true, so only the
-    range decides, and adding it is cheap."""
-    return BloomFilter(np.zeros(1, np.uint64), 0, 64)
-
-
-def dev_lists(ls, dq, n, cap=None, key_len=16, offsets=None, stream=None, work=None):
-    """probe_lists_dev into fresh tensors: starts pre-filled with -1, index
-    (cap entries; None: sized by a counting call) with POISON.  Returns
-    (starts uint64, index uint32 [cap]) on the host, the whole index buffer."""
-    import torch
-
-    G = ls.total_tables()
-    dev = dq.device
-    if work is None:
-        work = torch.empty(max(ls.lists_work_bytes(n), 1), dtype=torch.uint8, device=dev)
-    starts = torch.full((G + 1,), -1, dtype=torch.int64, device=dev)
-    if cap is None:
-        torch.cuda.synchronize()
-        ls.probe_lists_dev(dq, n, starts, None, work, offsets=offsets, key_len=key_len, stream=stream)
-        torch.cuda.synchronize()
-        cap = int(starts[G].item())
-        starts.fill_(-1)
-    index = torch.full((max(cap, 1),), POISON - (1 << 32), dtype=torch.int32, device=dev)
-    torch.cuda.synchronize()
-    ls.probe_lists_dev(dq, n, starts, index[:cap] if cap else None, work, offsets=offsets, key_len=key_len,
-                       stream=stream)
-    torch.cuda.synchronize()
-    return starts.cpu().numpy().view(np.uint64), index.cpu().numpy().view(np.uint32)[:cap]
 
 
 @pytest.fixture(scope="module")
@@ -493,6 +419,6 @@ def test_lset_lists_contract(ctx, quantile_set):
 
 @pytest.mark.gpu
 def test_cpp_mirror_level_set_lists_gpu():
-    r = subprocess.run([_cpp_bin(), "--gpu"], capture_output=True, text=True, timeout=300)
+    r = subprocess.run([cpp_bin("lset_lists_test"), "--gpu"], capture_output=True, text=True, timeout=300)
     assert r.returncode == 0, r.stdout + r.stderr
     assert "FAIL" not in r.stdout

@@ -17,11 +17,8 @@ import pytest
 import keygen
 import lsmbloom
 from lsmbloom import LevelSet
-from test_lset import expected_ids
-from test_lset_lists import check_lists, lists_from_ids
-from test_lset_repack_host import cpp_bin
-from test_lset_version import expected_mask
-from test_lset_versions import CHUNK, SST, batch_args, mk, queries
+from lset_support import (CHUNK, SST, batch_args, check_lists, cpp_bin, edit_queries, expected_ids, expected_mask,
+                          lists_from_ids, mk)
 
 L0 = lsmbloom.LSMB_LSET_ROW_L0
 ALL = lsmbloom.LSMB_LSET_REPACK_ALL
@@ -87,7 +84,7 @@ def test_copy_kernel_moves_every_segment_and_nothing_else(lens):
 
 @pytest.mark.gpu
 def test_cpp_mirror_repack_gpu():
-    r = subprocess.run([cpp_bin(), "--gpu"], capture_output=True, text=True, timeout=300)
+    r = subprocess.run([cpp_bin("lset_repack_mirror_test"), "--gpu"], capture_output=True, text=True, timeout=300)
     assert r.returncode == 0, r.stdout + r.stderr
     assert "FAIL" not in r.stdout
 
@@ -135,7 +132,7 @@ def _expect(oracle, rows, l0, q):
 def test_packed_chain_holds_one_chunk_and_answers_as_the_plain_chain(oracle):
     rows, l0 = _base(oracle)
     rng = np.random.default_rng(41)
-    q = queries(rows + [l0], rng, 150 * 40, 700)
+    q = edit_queries(rows + [l0], rng, 150 * 40, 700)
     ctx = lsmbloom.Context(0)
     base = LevelSet(ctx)
     base.add_many(*batch_args(oracle, [(r, t) for r, row in enumerate(rows) for t in row] + [(L0, t) for t in l0]))
@@ -196,7 +193,7 @@ def test_packed_child_and_parent_outlive_each_other(oracle):
     rows = [[mk(oracle, 100 * (r + 1) + t, 40 * r + 150 * t, *SST) for t in range(12)] for r in range(2)]
     l0 = [mk(oracle, 900 + j, 300 + 75 * j, *SST) for j in range(3)]
     rng = np.random.default_rng(42)
-    q = queries(rows + [l0], rng, 150 * 14, 500)
+    q = edit_queries(rows + [l0], rng, 150 * 14, 500)
     exp = _expect(oracle, rows, l0, q)
     ctx = lsmbloom.Context(0)
 
@@ -240,7 +237,7 @@ def test_threshold_moves_the_sparse_chunk_and_shares_the_dense_one(oracle):
     lone = mk(oracle, 77, 150 * 10, *SST)
     rows = [dense + [lone]]
     rng = np.random.default_rng(43)
-    q = queries(rows, rng, 150 * 13, 400)
+    q = edit_queries(rows, rng, 150 * 13, 400)
     ctx = lsmbloom.Context(0)
     grand = LevelSet(ctx)
     grand.add_many(*batch_args(oracle, [(0, t) for t in dense]))
@@ -291,7 +288,7 @@ def test_filter_in_a_chunk_of_its_own_moves_only_under_all(oracle):
     rows = [small + [big]]
     rng = np.random.default_rng(44)
     members = [b"user%08d" % i for i in range(150 * 5, 150 * 5 + 100)]
-    q = queries(rows, rng, 150 * 8, 300) + members
+    q = edit_queries(rows, rng, 150 * 8, 300) + members
     exp = _expect(oracle, rows, [], q)
     assert (exp[1][0] == 500).sum() >= 60  # its members hit
     ctx = lsmbloom.Context(0)

@@ -9,6 +9,7 @@ import numpy as np
 
 import lsmbloom
 from lsmbloom import LevelSet
+from lset_support import cpp_bin
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 vp = ctypes.c_void_p
@@ -31,18 +32,10 @@ def test_repack_plan_and_items_host(tmp_path):
     assert "all passed" in r.stdout
 
 
-CPP_BIN = os.path.join(ROOT, "storage-engine_amd", "build", "lset_repack_mirror_test")
-
-
-def cpp_bin():
-    if not os.path.exists(CPP_BIN):
-        subprocess.run(["make", "-s", "-C", os.path.join(ROOT, "storage-engine_amd"), "build/lset_repack_mirror_test"],
-                       check=True)
-    return CPP_BIN
 
 
 def test_cpp_mirror_repack_argument_checks():
-    r = subprocess.run([cpp_bin()], capture_output=True, text=True, timeout=300)
+    r = subprocess.run([cpp_bin("lset_repack_mirror_test")], capture_output=True, text=True, timeout=300)
     assert r.returncode == 0, r.stdout + r.stderr
 
 

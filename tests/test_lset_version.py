@@ -11,9 +11,7 @@ Python's bytes ordering (the same lexicographic order as Rust's [u8]); expected
 ids from expected_ids of tests/test_lset.py; never from the library.  Every
 comparison is exact equality over all answers.
 """
-import bisect
 import ctypes
-import functools
 import os
 import subprocess
 
@@ -23,37 +21,15 @@ import pytest
 import keygen
 import lsmbloom
 from lsmbloom import BloomFilter, FilterSet, LevelSet
-from test_lset import SIZINGS, add_tables, build_table, expected_ids
+from lset_support import (SIZINGS, add_tables, build_table, cpp_bin, expected_ids, expected_mask, k12, kvar, l0_ranges,
+                          l0_tables, low_bits, queries, reference, row_tables)
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CPP_BIN = os.path.join(ROOT, "storage-engine_amd", "build", "lset_version_test")
 NONE = lsmbloom.LSMB_LSET_NONE
 L0 = lsmbloom.LSMB_LSET_ROW_L0
 EINVAL = lsmbloom.LSMB_EINVAL
 vp = ctypes.c_void_p
 SST = (1000, 0.01)
-
-
-def expected_mask(oracle, tabs, keys):
-    """tabs: the L0 tables in position order, (table_id, words, num_bits, k,
-    lo, hi) with any overlap -> (mask, in-range mask), uint64 [len(keys)] each."""
-    assert len(tabs) <= 64
-    if not tabs or not keys:
-        return np.zeros(len(keys), dtype=np.uint64), np.zeros(len(keys), dtype=np.uint64)
-    data, offs = keygen.pack(keys)
-    bits = oracle.probe([(t[1], t[2], t[3]) for t in tabs], data, offs)  # [n, ceil(F/8)], bit f%8 of byte f/8
-    wide = np.zeros((len(keys), 8), dtype=np.uint8)
-    wide[:, :bits.shape[1]] = bits
-    may = wide.view("<u8").reshape(-1)
-    order = sorted(range(len(keys)), key=lambda i: keys[i])
-    sk = [keys[i] for i in order]
-    idx = np.array(order, dtype=np.int64)
-    inr = np.zeros(len(keys), dtype=np.uint64)
-    for j, t in enumerate(tabs):
-        a, b = bisect.bisect_left(sk, t[4]), bisect.bisect_right(sk, t[5])  # min_j <= key <= max_j
-        if a < b:
-            inr[idx[a:b]] |= np.uint64(1 << j)
-    return may & inr, inr
 
 
 # ---------------------------------------------------------------- without a GPU
@@ -95,163 +71,20 @@ def test_fset_plan_host(tmp_path):
     assert "all passed" in r.stdout
 
 
-def _cpp_bin():
-    if not os.path.exists(CPP_BIN):
-        subprocess.run(["make", "-s", "-C", os.path.join(ROOT, "storage-engine_amd"), "build/lset_version_test"],
-                       check=True)
-    return CPP_BIN
-
-
 def test_cpp_mirror_version_argument_checks():
-    r = subprocess.run([_cpp_bin()], capture_output=True, text=True, timeout=300)
+    r = subprocess.run([cpp_bin("lset_version_test")], capture_output=True, text=True, timeout=300)
     assert r.returncode == 0, r.stdout + r.stderr
 
 
 # ------------------------------------------------------------------- on the GPU
 #
-# The parity workload: ids 0 .. 9999 as keys "user%08d" (12 bytes), the same
-# plus four digits (16 bytes) and the same plus "abcd" and a run of x (16 .. 40
-# bytes, so the keys of one id share their first 16).  64 L0 tables over that
-# space, the special ranges first so that every T0 >= 8 holds them.
-
-def k12(i):
-    return b"user%08d" % i
-
-
-def k16(i, tail):
-    return b"user%08d%04d" % (i, tail)
-
-
-def kvar(i, r):
-    return b"user%08d" % i + b"abcd" + b"x" * r
-
-
-def l0_ranges():
-    rng = np.random.default_rng(61)
-    rg = [None] * 64
-    rg[0] = (k12(2000), k12(5000))
-    rg[1] = (b"user", b"user\xff")                                          # spans every key of the workload
-    rg[2] = rg[0]                                                           # identical ranges
-    rg[3] = (k12(2500), k12(2600))                                          # nested
-    rg[4] = (rg[0][1], k12(5200))                                           # touches table 0 at one key
-    rg[5] = (b"", k12(3000))                                                # an empty-string bound
-    rg[6] = (b"user00004000abcdAA", b"user00004000abcd" + b"zz" * 5)        # long bounds sharing their first 16
-    rg[7] = (k12(4100), k12(4100))                                          # one key
-    for j in range(8, 64):
-        a = int(rng.integers(0, 9000))
-        rg[j] = (k12(a), k12(a + int(rng.integers(1, 3000))) + (b"9999" if j % 3 == 0 else b""))
-    return rg
-
-
-def sizing_of(geom, j):
-    """(num_bits, k) of L0 table j: all SST-sized, or mixed over SIZINGS with
-    one filter of no hash (table 5: only its range decides)."""
-    if geom == "sst":
-        return lsmbloom.params(*SST)
-    nb, k = lsmbloom.params(*SIZINGS[j % 4])
-    return (nb, 0) if j == 5 else (nb, k)
-
-
-@functools.lru_cache(maxsize=None)
-def l0_tables(geom):
-    import oracle_ct
-    oracle = oracle_ct.load()
-    rng = np.random.default_rng(62)
-    tabs, members = [], []
-    for j, (lo, hi) in enumerate(l0_ranges()):
-        a = int(lo[4:12]) if len(lo) >= 12 else 0
-        b = int(hi[4:12]) if len(hi) >= 12 and hi[4:12].isdigit() else 9999
-        ids = rng.integers(a, b + 1, 400)
-        cand = [k12(i) for i in ids] + [k16(i, i * 7 % 10000) for i in ids] + [kvar(i, i % 25) for i in ids]
-        cand += [lo, hi, lo + b"\x00", lo + b"zz"]
-        mem = sorted({c for c in cand if lo <= c <= hi})
-        assert mem
-        nb, k = sizing_of(geom, j)
-        data, offs = keygen.pack(mem)
-        tabs.append((7000 + j, oracle.build_var(data, offs, nb, k), nb, k, lo, hi))
-        members.append(frozenset(mem))
-    return tabs, members
-
-
-@functools.lru_cache(maxsize=None)
-def row_tables():
-    """Three rows: 65 tables, 5 and 3, disjoint within a row."""
-    import oracle_ct
-    oracle = oracle_ct.load()
-    rows = []
-    for r, ntab in enumerate((65, 5, 3)):
-        tabs = []
-        width = 10000 // ntab
-        for t in range(ntab):
-            ids = range(t * width + r, t * width + width - 20, 3)
-            keys = sorted([k12(i) for i in ids] + [kvar(i, i % 25) for i in ids][::2] + [k16(i, i * 7 % 10000) for i in ids][::2])
-            tabs.append(build_table(oracle, 100 * (r + 1) + t, keys, SIZINGS[(t + r) % 4]))
-        rows.append(tabs)
-    return rows
-
-
-@functools.lru_cache(maxsize=None)
-def queries(kind):
-    """5000 keys of one kind, shuffled (every prefix of them is a fair sample)."""
-    rng = np.random.default_rng({"fixed16": 63, "fixed12": 64, "var": 65}[kind])
-    tabs, members = l0_tables("sst")
-    ids = [int(i) for i in rng.integers(0, 11000, 5000)]
-    if kind == "fixed16":
-        q = [k16(i, int(t)) for i, t in zip(ids[:3000], rng.integers(0, 10000, 3000))]
-        q += [k16(i, i * 7 % 10000) for i in ids[3000:4600]]           # the members' form
-        q += [b"zzzz%012d" % i for i in ids[:100]]                     # outside every range
-        pool = [m for mem in members for m in mem if len(m) == 16]
-    elif kind == "fixed12":
-        q = [k12(i) for i in ids[:4500]] + [b"zzzz%08d" % i for i in ids[:100]]
-        pool = [m for mem in members for m in mem if len(m) == 12]
-    else:
-        q = [kvar(i, int(r)) for i, r in zip(ids[:2500], rng.integers(0, 25, 2500))]
-        q += [k12(i) for i in ids[2500:3200]] + [k16(i, i * 7 % 10000) for i in ids[3200:3600]]
-        q += [b"", b"u", b"user", b"user0000", b"zzz", b"\xff" * 40, b"user00004000abcd", b"user00004000abcdAA",
-              b"user00004000abcdA", b"user00004000abcdzzzzzzzzzzz", b"user00004000abcdzzzzzzzzz"]
-        for t in tabs:
-            q += [t[4], t[5], t[4][:-1], t[5] + b"\x00", t[5][:16], t[4] + b"\xff"]
-        pool = [m for mem in members for m in mem]
-    q += [pool[int(i)] for i in rng.integers(0, len(pool), 5000 - len(q))]
-    assert len(q) == 5000
-    q = [q[int(i)] for i in rng.permutation(5000)]
-    if kind != "var":
-        assert len({len(x) for x in q}) == 1
-    else:
-        assert min(len(x) for x in q) == 0 and max(len(x) for x in q) == 40
-    return q
-
-
-@functools.lru_cache(maxsize=None)
-def reference(geom, kind):
-    """(mask of all 64 tables, ids of the three rows) for queries(kind): bit j
-    depends on table j alone, so the first T0 tables' answer is the low T0 bits."""
-    import oracle_ct
-    oracle = oracle_ct.load()
-    tabs, members = l0_tables(geom)
-    q = queries(kind)
-    mask, inr = expected_mask(oracle, tabs, q)
-    ids = expected_ids(oracle, row_tables(), q)
-    # the inputs exercise what they should (over the first 8 tables, which every T0 >= 8 holds)
-    low = np.uint64(0xFF)
-    assert ((inr & ~mask & low) != 0).any(), "no key in range of a table and masked out by its filter"
-    assert any(bin(int(m) & 0xFF).count("1") >= 2 for m in mask), "no key with two bits set"
-    assert (inr == 0).any(), "no key outside every L0 range"
-    assert any((int(m) >> j) & 1 and x not in members[j] for x, m in zip(q, mask) for j in range(8)), "no false positive"
-    mask.setflags(write=False)
-    ids.setflags(write=False)
-    return mask, ids
-
+# The parity workload (l0_tables, row_tables, queries, reference) is lset_support's.
 
 def probe_kind(ls, kind, q):
     if kind == "var":
         return ls.probe_version_keys(q)
     data = np.frombuffer(b"".join(q), dtype=np.uint8)
     return ls.probe_version(data, key_len=16 if kind == "fixed16" else 12)
-
-
-def low_bits(mask, t0):
-    return mask if t0 == 64 else mask & np.uint64((1 << t0) - 1)
 
 
 @pytest.mark.gpu
@@ -634,6 +467,6 @@ def test_rows_only_entry_points_ignore_l0(oracle):
 
 @pytest.mark.gpu
 def test_cpp_mirror_version_gpu():
-    r = subprocess.run([_cpp_bin(), "--gpu"], capture_output=True, text=True, timeout=300)
+    r = subprocess.run([cpp_bin("lset_version_test"), "--gpu"], capture_output=True, text=True, timeout=300)
     assert r.returncode == 0, r.stdout + r.stderr
     assert "FAIL" not in r.stdout

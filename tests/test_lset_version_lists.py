@@ -23,12 +23,10 @@ import pytest
 import keygen
 import lsmbloom
 from lsmbloom import LevelSet
-from test_lset import add_tables, build_table, expected_ids
-from test_lset_lists import POISON, always_maybe, check_lists, lists_from_ids
-from test_lset_version import expected_mask, l0_tables, low_bits, queries, reference, row_tables
+from lset_support import (POISON, add_tables, always_maybe, build_table, check_lists, cpp_bin, dev_lists, expected_ids,
+                          expected_mask, l0_tables, lists_from_ids, low_bits, queries, reference, row_tables)
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CPP_BIN = os.path.join(ROOT, "storage-engine_amd", "build", "lset_version_lists_test")
 PLAN_SRC = os.path.join(ROOT, "tests", "cpp", "lset_vlists_plan_test.cpp")
 NONE = lsmbloom.LSMB_LSET_NONE
 L0 = lsmbloom.LSMB_LSET_ROW_L0
@@ -120,15 +118,8 @@ def test_lset_vlists_plan_and_reference_host(tmp_path, flags):
     assert "all passed" in r.stdout
 
 
-def _cpp_bin():
-    if not os.path.exists(CPP_BIN):
-        subprocess.run(["make", "-s", "-C", os.path.join(ROOT, "storage-engine_amd"), "build/lset_version_lists_test"],
-                       check=True)
-    return CPP_BIN
-
-
 def test_cpp_mirror_version_lists_argument_checks():
-    r = subprocess.run([_cpp_bin()], capture_output=True, text=True, timeout=300)
+    r = subprocess.run([cpp_bin("lset_version_lists_test")], capture_output=True, text=True, timeout=300)
     assert r.returncode == 0, r.stdout + r.stderr
 
 
@@ -400,7 +391,6 @@ def test_version_lists_skew(ctx):
 @pytest.mark.gpu
 def test_version_lists_degenerate_sets(ctx, oracle, small_set):
     import torch
-    from test_lset_lists import dev_lists
 
     base, q, mask, ids = small_set
     dev = "cuda:0"
@@ -588,6 +578,6 @@ def test_version_lists_after_edits(ctx, oracle):
 
 @pytest.mark.gpu
 def test_cpp_mirror_version_lists_gpu():
-    r = subprocess.run([_cpp_bin(), "--gpu"], capture_output=True, text=True, timeout=300)
+    r = subprocess.run([cpp_bin("lset_version_lists_test"), "--gpu"], capture_output=True, text=True, timeout=300)
     assert r.returncode == 0, r.stdout + r.stderr
     assert "FAIL" not in r.stdout

@@ -20,47 +20,12 @@ import pytest
 import keygen
 import lsmbloom
 from lsmbloom import LevelSet
-from test_lset import expected_ids
-from test_lset_lists import check_lists, lists_from_ids
+from lset_support import (CHUNK, SST, batch_args, block, check_lists, cpp_bin, edit_queries, expected_ids, lists_from_ids,
+                          mk)
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NONE = lsmbloom.LSMB_LSET_NONE
 vp = ctypes.c_void_p
-CHUNK = 4 << 20  # the arena's chunk (include/lsmbloom.h)
-SST = lsmbloom.params(1000, 0.01)  # SSTableBuilder's filter
-
-
-def mk(oracle, tid, first, nb, k, nkeys=40):
-    """(table_id, words, num_bits, k, min_key, max_key): nkeys keys out of the
-    100 ids from `first`, in a filter of exactly (nb, k)."""
-    rng = np.random.default_rng(1000 + tid)
-    ids = np.sort(rng.choice(100, size=nkeys, replace=False)) + first
-    keys = [b"user%08d" % i for i in ids]
-    data, offs = keygen.pack(keys)
-    w = oracle.build_var(data, offs, nb, k) if nb else np.zeros(0, np.uint64)
-    return (tid, w, nb, k, keys[0], keys[-1])
-
-
-def block(oracle, t):
-    return oracle.serialize(t[1] if t[2] else np.zeros(1, np.uint64), t[2], t[3])
-
-
-def batch_args(oracle, placed):
-    """placed: [(row, table)] -> the arguments of LevelSet.add_many (no CRCs)."""
-    return ([r for r, _ in placed], [t[0] for _, t in placed], [block(oracle, t) for _, t in placed],
-            [(t[4], t[5]) for _, t in placed])
-
-
-def queries(rows, rng, span, nrand):
-    """Members' neighbours, random ids over the whole span, every bound and the keys just outside it."""
-    tabs = [t for row in rows for t in row]
-    q = [b"user%08d" % i for i in rng.integers(0, span, nrand)]
-    q += [t[4] for t in tabs] + [t[5] for t in tabs]
-    q += [t[4][:-1] for t in tabs] + [t[5] + b"\x00" for t in tabs]
-    q += [b"", b"user", b"\xff" * 40]
-    return q
-
-
 def check_probe(ls, oracle, rows, q, what=""):
     """Var-len keys through probe_keys, and the 12-byte ones again as fixed-length keys."""
     exp = expected_ids(oracle, rows, q)
@@ -156,18 +121,10 @@ def test_version_entry_points_are_exported_and_reject_null():
     assert L.lsmb_abi_version() == 6
 
 
-CPP_BIN = os.path.join(ROOT, "storage-engine_amd", "build", "lset_versions_test")
-
-
-def _cpp_bin():
-    if not os.path.exists(CPP_BIN):
-        subprocess.run(["make", "-s", "-C", os.path.join(ROOT, "storage-engine_amd"), "build/lset_versions_test"],
-                       check=True)
-    return CPP_BIN
 
 
 def test_cpp_mirror_version_argument_checks():
-    r = subprocess.run([_cpp_bin()], capture_output=True, text=True, timeout=300)
+    r = subprocess.run([cpp_bin("lset_versions_test")], capture_output=True, text=True, timeout=300)
     assert r.returncode == 0, r.stdout + r.stderr
 
 
@@ -219,7 +176,7 @@ def test_segmented_crc_kernel_matches_zlib():
 
 @pytest.mark.gpu
 def test_cpp_mirror_versions_gpu():
-    r = subprocess.run([_cpp_bin(), "--gpu"], capture_output=True, text=True, timeout=300)
+    r = subprocess.run([cpp_bin("lset_versions_test"), "--gpu"], capture_output=True, text=True, timeout=300)
     assert r.returncode == 0, r.stdout + r.stderr
     assert "FAIL" not in r.stdout
 
@@ -259,7 +216,7 @@ def test_batch_load_equals_the_per_table_loop(oracle, two_rows):
     nwords = [(t[2] + 63) // 64 for _, t in placed]
     touched = arena_chunks(nwords)
     assert 2 <= touched <= 3  # the first chunk, the large filter's own and, unless it came last, one more
-    q = queries(rows, rng, 150 * 36 + 200, 3000)
+    q = edit_queries(rows, rng, 150 * 36 + 200, 3000)
     assert len(q) <= 4000
     ctx = lsmbloom.Context(0)
     loop = LevelSet(ctx)
@@ -351,7 +308,7 @@ def test_batch_corruption_is_all_or_nothing(oracle, two_rows):
     assert (ls.tables(0), ls.tables(1)) == (before[0] + 3, before[1] + 3)
     ls.seal()
     mine = [rows[0][:3] + [t for r, t in placed if r == 0], [t for r, t in placed if r == 1]]
-    check_probe(ls, oracle, mine, queries(mine, np.random.default_rng(32), 150 * 8, 1500), "after the refusals")
+    check_probe(ls, oracle, mine, edit_queries(mine, np.random.default_rng(32), 150 * 8, 1500), "after the refusals")
     ls.close()
     ctx.close()
 
@@ -377,7 +334,7 @@ def test_derive_shares_the_parent_and_outlives_it(oracle):
     h = vp()
     assert L.lsmb_lset_derive(parent.h, None, 3, None, ctypes.byref(h)) == lsmbloom.LSMB_EINVAL and h.value is None
     assert L.lsmb_lset_derive(parent.h, None, 0, None, None) == lsmbloom.LSMB_EINVAL
-    q = queries(rows, rng, 150 * 41 + 200, 2500)
+    q = edit_queries(rows, rng, 150 * 41 + 200, 2500)
     check_probe(parent, oracle, rows, q, "parent")
     s_parent = parent.stats()
     drops = [777, 103, 215, 239, 99999]  # 777 twice, 99999 absent
@@ -433,7 +390,7 @@ def test_derive_shares_the_parent_and_outlives_it(oracle):
 def test_chain_of_six_versions_lets_go_of_the_first(oracle):
     tabs = [mk(oracle, t, 150 * t, *SST) for t in range(12)]
     rng = np.random.default_rng(34)
-    q = queries([tabs], rng, 150 * 20, 1500)
+    q = edit_queries([tabs], rng, 150 * 20, 1500)
     ctx = lsmbloom.Context(0)
     cur = LevelSet(ctx)
     cur.add_many(*batch_args(oracle, [(0, t) for t in tabs]))
@@ -468,7 +425,7 @@ def test_chain_of_six_versions_lets_go_of_the_first(oracle):
 def test_bad_edit_leaves_the_child_unsealed_and_the_parent_whole(oracle):
     tabs = [mk(oracle, 10 + t, 150 * t, *SST) for t in range(6)]
     rng = np.random.default_rng(35)
-    q = queries([tabs], rng, 150 * 8, 1200)
+    q = edit_queries([tabs], rng, 150 * 8, 1200)
     ctx = lsmbloom.Context(0)
     parent = LevelSet(ctx)
     parent.add_many(*batch_args(oracle, [(0, t) for t in tabs]))
