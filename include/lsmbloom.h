@@ -882,6 +882,93 @@ int lsmb_lset_probe_version_lists_dev(lsmb_lset* ls, const void* d_data, const v
 int lsmb_lset_probe_version_lists(lsmb_lset* ls, const uint8_t* data, const uint64_t* offsets, uint32_t key_len,
                                   uint64_t n, uint64_t* starts, uint32_t* index, uint64_t cap);
 
+/* ---- the walk itself: each key's first candidate ---------------------------- */
+/* DB::get and Snapshot::get visit the tables of a Version in one fixed order and
+ * STOP at the first one that holds the key, value or tombstone
+ * (src/db/mod.rs:243-267, src/db/snapshot.rs:40-69).  The lists above name every
+ * table that may hold a key, so a reader working from them also reads the older
+ * copies of an overwritten key, which the store itself never does.  WALK STEPS:
+ * with T0 = lsmb_lset_l0_tables(ls) and R = lsmb_lset_rows(ls),
+ *   step w <  T0     consults the L0 table at position T0-1-w: step 0 is the
+ *                    newest arrival, the order of version.level(0).iter().rev()
+ *                    (src/db/mod.rs:243);
+ *   step w = T0 + r  consults row r (src/db/mod.rs:255-267);
+ * W = T0 + R steps in all.  Key i has a CANDIDATE at an L0 step iff the bit of
+ * that position is set in lsmb_lset_probe_version's mask, at a row step iff
+ * lsmb_lset_probe answers a table in that row (src/sstable/reader.rs:192-199's
+ * range-and-bloom check either way; a row emptied by derive never has one).
+ * A multi-get works in rounds: probe; look the keys of each table's list up in
+ * that table; a key that was found is finished (from = LSMB_LSET_NONE), a false
+ * positive resumes one step later (from = step + 1); repeat until every step is
+ * LSMB_LSET_NONE.  The table lookups of all rounds together are exactly the
+ * SSTable::get calls DB::get would have made for those keys. */
+
+/* W (the steps of src/db/mod.rs:243-267's walk).  0 for NULL or an unsealed set. */
+uint32_t lsmb_lset_walk_steps(const lsmb_lset* ls);
+
+/* Per key, from one hash (src/db/mod.rs:243-267, src/db/snapshot.rs:40-69,
+ * src/sstable/reader.rs:192-199).  d_from is uint32_t[n], key i's resume step;
+ * NULL means all zero.
+ *   d_step[i]  uint32_t[n], may be NULL: the smallest step w >= d_from[i] at
+ *              which key i has a candidate, else LSMB_LSET_NONE;
+ *   d_ord[i]   uint32_t[n], required when n > 0: that candidate's Version
+ *              ordinal in lsmb_lset_version_order's numbering (T0-1-w for an L0
+ *              step, T0 + g for a row step, g the rows' ordinal), else
+ *              LSMB_LSET_NONE.
+ * d_from[i] >= W, LSMB_LSET_NONE included, answers LSMB_LSET_NONE in both and
+ * the key is neither read nor hashed: how a caller retires a resolved key.
+ * d_step may be d_from itself: a key's resume step is read before its step is
+ * written.  n == 0 writes nothing; W == 0 writes LSMB_LSET_NONE everywhere.
+ * LSMB_EINVAL (outputs untouched): a call before seal, a NULL d_ord or NULL
+ * keys with n > 0.  Asynchronous on `stream` (NULL: the context's), no host
+ * synchronisation, no scratch, no atomics: the sealed set stays read-only,
+ * probes on different streams need no ordering, and the same inputs give the
+ * same bytes on every run. */
+int lsmb_lset_probe_walk_dev(lsmb_lset* ls, const void* d_data, const void* d_offsets, uint32_t key_len, uint64_t n,
+                             const void* d_from, void* d_step, void* d_ord, void* stream);
+
+/* Host keys, resume steps and outputs; synchronous, through the context's
+ * staging as lsmb_lset_probe_version (src/db/mod.rs:243-267's walk, one round
+ * of it).  from and step may be NULL as above, or one array. */
+int lsmb_lset_probe_walk(lsmb_lset* ls, const uint8_t* data, const uint64_t* offsets, uint32_t key_len, uint64_t n,
+                         const uint32_t* from, uint32_t* step, uint32_t* ord);
+
+/* Bytes of device workspace a walk lists probe of n keys needs (one round of
+ * src/db/mod.rs:243-267's walk under src/sstable/reader.rs:192-199's checks keeps
+ * its per-key ordinals and their transposition there).  0 for NULL, an unsealed
+ * set, n == 0, V == 0 or n > 2^32-1. */
+uint64_t lsmb_lset_walk_lists_work_bytes(const lsmb_lset* ls, uint64_t n);
+
+/* The same answer per table: d_starts is uint64_t[V + 1], d_index is
+ * uint32_t[cap], V = lsmb_lset_version_tables(ls).  For every Version ordinal
+ * v, d_index[d_starts[v] .. d_starts[v+1]) = the indices i, ascending, of the
+ * keys whose first candidate at or after d_from[i] is table v (the table
+ * src/db/mod.rs:243-267's walk, resumed there, reads next; checked as
+ * src/sstable/reader.rs:192-199).  A key is in at most one list, so
+ * d_starts[V] <= n.  d_from and d_step (optional) are lsmb_lset_probe_walk_dev's,
+ * aliasing included.  Capacity, counting calls, errors, streams, scratch and
+ * determinism are lsmb_lset_probe_version_lists_dev's with
+ * lsmb_lset_walk_lists_work_bytes for the workspace: d_starts is always exact;
+ * the entry at global position p is written iff p < cap and nothing else in
+ * d_index is touched; n == 0 or V == 0 writes V + 1 zero starts (and
+ * LSMB_LSET_NONE in every d_step[i] when it is given) and nothing else;
+ * LSMB_EINVAL (outputs untouched) for n > 2^32-1, V > 2^32-1, a call before
+ * seal, null outputs, and with n > 0 && V > 0 a null or not 16-byte-aligned
+ * d_work or work_bytes below the need.  No atomics: the same inputs give the
+ * same bytes on every run. */
+int lsmb_lset_probe_walk_lists_dev(lsmb_lset* ls, const void* d_data, const void* d_offsets, uint32_t key_len,
+                                   uint64_t n, const void* d_from, void* d_step, void* d_starts, void* d_index,
+                                   uint64_t cap, void* d_work, uint64_t work_bytes, void* stream);
+
+/* Host keys, resume steps and outputs (step[n] optional, starts[V + 1],
+ * index[cap]); synchronous; one round of src/db/mod.rs:243-267's walk
+ * (src/db/snapshot.rs:40-69) under src/sstable/reader.rs:192-199's checks as
+ * above.  The workspace is the context's own scratch, as
+ * lsmb_lset_probe_version_lists; the resume steps go up next to the keys, and
+ * only starts, the steps and min(total, cap) entries cross PCIe on the way back. */
+int lsmb_lset_probe_walk_lists(lsmb_lset* ls, const uint8_t* data, const uint64_t* offsets, uint32_t key_len, uint64_t n,
+                               const uint32_t* from, uint32_t* step, uint64_t* starts, uint32_t* index, uint64_t cap);
+
 /* ---- introspection ------------------------------------------------------- */
 
 /* Name of the device build strategy the dispatcher picks for (num_bits, k, n):

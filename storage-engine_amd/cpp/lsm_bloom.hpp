@@ -516,6 +516,81 @@ class LevelSet {
                                                 work_bytes, stream));
     }
 
+    // The walk itself (lsmb_lset_probe_walk): DB::get stops at the first table
+    // that holds the key (src/db/mod.rs:243-267).  Step w < l0_tables()
+    // consults the L0 table at position l0_tables() - 1 - w (step 0 the
+    // newest), step l0_tables() + r row r; walk_steps() in all.  Per key: the
+    // first step at or after its resume step (`from`, null: 0) with a
+    // candidate and that table's Version ordinal, LSMB_LSET_NONE in both when
+    // there is none or the resume step is >= walk_steps() (a retired key).
+    // A multi-get repeats the probe with from = step + 1 for the false
+    // positives and from = LSMB_LSET_NONE for the keys it found.
+    uint32_t walk_steps() const { return lsmb_lset_walk_steps(ls_); }
+    struct WalkAnswer {
+        std::vector<uint32_t> step, ord;  // n each
+    };
+    // Packed host keys: offsets null selects fixed-length keys of key_len bytes.
+    WalkAnswer probe_walk(const uint8_t* data, const uint64_t* offsets, uint32_t key_len, uint64_t n,
+                          const std::vector<uint32_t>* from = nullptr) {
+        if (from && from->size() != n) throw std::invalid_argument("probe_walk: one resume step per key");
+        WalkAnswer a;
+        a.step.resize(n);
+        a.ord.resize(n);
+        uint32_t none = 0;
+        check(lsmb_lset_probe_walk(ls_, data, offsets, key_len, n, from && n ? from->data() : nullptr,
+                                   n ? a.step.data() : &none, n ? a.ord.data() : &none));
+        return a;
+    }
+    WalkAnswer probe_walk_keys(const std::vector<std::string>& keys, const std::vector<uint32_t>* from = nullptr) {
+        const detail::PackedKeys pk = detail::pack_keys(keys);
+        return probe_walk(pk.bytes(), pk.offs.data(), 0, keys.size(), from);
+    }
+    // Device keys, resume steps (d_from, may be null) and outputs (d_step: n
+    // uint32_t, may be null or d_from itself; d_ord: n uint32_t),
+    // asynchronous on `stream`.
+    void probe_walk_dev(const void* d_data, const void* d_offsets, uint32_t key_len, uint64_t n, const void* d_from,
+                        void* d_step, void* d_ord, void* stream = nullptr) {
+        check(lsmb_lset_probe_walk_dev(ls_, d_data, d_offsets, key_len, n, d_from, d_step, d_ord, stream));
+    }
+    // The same answer per table: index[starts[v] .. starts[v+1]) = the
+    // ascending indices of the keys whose first candidate is Version ordinal
+    // v; a key is in at most one list.  A counting call sizes the index.
+    struct WalkLists {
+        std::vector<uint64_t> starts;  // version_tables() + 1
+        std::vector<uint32_t> index;
+        std::vector<uint32_t> step;  // n
+    };
+    WalkLists probe_walk_lists(const uint8_t* data, const uint64_t* offsets, uint32_t key_len, uint64_t n,
+                               const std::vector<uint32_t>* from = nullptr) {
+        if (from && from->size() != n) throw std::invalid_argument("probe_walk_lists: one resume step per key");
+        WalkLists out;
+        out.starts.assign(version_tables() + 1, 0);
+        out.step.resize(n);
+        uint32_t none = 0;
+        const uint32_t* f = from && n ? from->data() : nullptr;
+        uint32_t* s = n ? out.step.data() : &none;
+        check(lsmb_lset_probe_walk_lists(ls_, data, offsets, key_len, n, f, s, out.starts.data(), nullptr, 0));
+        out.index.resize(out.starts.back());
+        if (!out.index.empty())
+            check(lsmb_lset_probe_walk_lists(ls_, data, offsets, key_len, n, f, s, out.starts.data(), out.index.data(),
+                                             out.index.size()));
+        return out;
+    }
+    WalkLists probe_walk_lists_keys(const std::vector<std::string>& keys, const std::vector<uint32_t>* from = nullptr) {
+        const detail::PackedKeys pk = detail::pack_keys(keys);
+        return probe_walk_lists(pk.bytes(), pk.offs.data(), 0, keys.size(), from);
+    }
+    // Device keys, resume steps, outputs (d_step optional; d_starts:
+    // version_tables() + 1 uint64_t; d_index: cap uint32_t) and workspace
+    // (walk_lists_work_bytes(n) bytes), asynchronous on `stream`.
+    uint64_t walk_lists_work_bytes(uint64_t n) const { return lsmb_lset_walk_lists_work_bytes(ls_, n); }
+    void probe_walk_lists_dev(const void* d_data, const void* d_offsets, uint32_t key_len, uint64_t n,
+                              const void* d_from, void* d_step, void* d_starts, void* d_index, uint64_t cap,
+                              void* d_work, uint64_t work_bytes, void* stream = nullptr) {
+        check(lsmb_lset_probe_walk_lists_dev(ls_, d_data, d_offsets, key_len, n, d_from, d_step, d_starts, d_index, cap,
+                                             d_work, work_bytes, stream));
+    }
+
    private:
     explicit LevelSet(lsmb_lset* h) : ls_(h) {}  // derive
     static const uint8_t* u8(std::string_view s) { return reinterpret_cast<const uint8_t*>(s.data()); }

@@ -2,11 +2,11 @@
 // Host-side plumbing only; the placement of filters in the arena is planned in
 // lset_arena.hpp, a repacking derive in lset_repack.hpp; the kernels are in
 // lset.hip, lset_lists.hip, lset_version.hip, lset_version_lists.hip,
-// lset_repack.hip and crc32.hip.  Every add stages, copies and commits through
-// lset_stage / lset_commit (a repacking derive through lset_commit_arena); the
-// four lists entry points describe their flavour (LsetListsProbe) and run one
-// device path (lset_lists_dev) or one host path (lset_lists_host, whose
-// copy-back is ctx.hpp's lists_to_host).
+// lset_walk_first.hip, lset_repack.hip and crc32.hip.  Every add stages, copies
+// and commits through lset_stage / lset_commit (a repacking derive through
+// lset_commit_arena); the six lists entry points describe their flavour
+// (LsetListsProbe) and run one device path (lset_lists_dev) or one host path
+// (lset_lists_host, whose copy-back is ctx.hpp's lists_to_host).
 #include <string.h>
 
 #include <algorithm>
@@ -23,6 +23,7 @@
 #include "lset_order.hpp"
 #include "lset_repack.hpp"
 #include "lset_vlists_plan.hpp"
+#include "lset_walk_plan.hpp"
 
 using namespace lsmb;
 
@@ -876,34 +877,53 @@ uint64_t lsmb_lset_lists_work_bytes(const lsmb_lset* ls, uint64_t n) {
     return lset_lists_plan(n, ls->nrows, ls->base[ls->nrows]).work_bytes;
 }
 
-// A lists probe over this sealed set, the rows' (lsmb_lset_probe_lists*) or the
-// whole Version's (lsmb_lset_probe_version_lists*): what the two flavours differ
-// in.  A Version without L0 tables is the rows' probe, byte for byte.
+// A lists probe over this sealed set, the rows' (lsmb_lset_probe_lists*), the
+// whole Version's (lsmb_lset_probe_version_lists*) or the walk's
+// (lsmb_lset_probe_walk_lists*): what the flavours differ in.  A Version
+// without L0 tables is the rows' probe, byte for byte.
+enum class LsetLists { Rows, Version, Walk };
 struct LsetListsProbe {
     uint64_t total = 0;       // tables: the starts have total + 1 entries
     uint64_t work_bytes = 0;  // the workspace of n keys
     uint64_t bound = 0;       // no more list entries than this
     const char* sizer = "";   // the public function that reports work_bytes
-    hipError_t (*launch)(lsmb_lset* ls, const KeyBatch& kb, uint64_t* d_starts, uint32_t* d_index, uint64_t cap,
-                         void* d_work, uint64_t work_bytes, hipStream_t st) = nullptr;
+    // the walk only: every key's resume step (null: all zero) and, coming back
+    // next to the lists, its step (null: not wanted); the caller's pointers,
+    // device memory on the device path, host memory on the host path
+    const uint32_t* from = nullptr;
+    uint32_t* step = nullptr;
+    hipError_t (*launch)(lsmb_lset* ls, const KeyBatch& kb, const uint32_t* d_from, uint32_t* d_step, uint64_t* d_starts,
+                         uint32_t* d_index, uint64_t cap, void* d_work, uint64_t work_bytes, hipStream_t st) = nullptr;
 };
 
-// The argument checks shared by all four lists entry points, then *lp.
-static int lset_lists_desc(const lsmb_lset* ls, bool version, uint64_t n, const void* starts, const void* index,
+// The argument checks shared by all six lists entry points, then *lp.
+static int lset_lists_desc(const lsmb_lset* ls, LsetLists kind, uint64_t n, const void* starts, const void* index,
                            uint64_t cap, LsetListsProbe* lp) {
     if (int rc = lset_probe_check(ls)) return rc;
     if (n > UINT32_MAX) return fail(LSMB_EINVAL, "more than 2^32-1 keys (the lists hold 32-bit indices)");
-    const uint64_t G = ls->base[ls->nrows], T0 = version ? ls->l0.size() : 0;
+    const uint64_t G = ls->base[ls->nrows], T0 = kind == LsetLists::Rows ? 0 : ls->l0.size();
     if (T0 + G > UINT32_MAX) return fail(LSMB_EINVAL, "more than 2^32-1 tables");
     if (!starts || (cap && !index)) return fail(LSMB_EINVAL, "null output");
     lp->total = T0 + G;
+    if (kind == LsetLists::Walk) {
+        lp->work_bytes = lset_walk_lists_plan(n, T0 + G).work_bytes;
+        lp->bound = n;  // a key is in at most one list
+        lp->sizer = "lsmb_lset_walk_lists_work_bytes";
+        lp->launch = [](lsmb_lset* ls, const KeyBatch& kb, const uint32_t* d_from, uint32_t* d_step, uint64_t* d_starts,
+                        uint32_t* d_index, uint64_t cap, void* d_work, uint64_t work_bytes, hipStream_t st) {
+            return launch_lset_walk_lists(kb, ls->rows, ls->base[ls->nrows], (const RangedFilter*)ls->l0_desc.p,
+                                          (uint32_t)ls->l0.size(), ls->l0_rg, ls->l0_cl, d_from, d_step, d_starts,
+                                          d_index, cap, d_work, work_bytes, ls->c->num_cus, st);
+        };
+        return LSMB_OK;
+    }
     if (T0 == 0) {
         const LsetListsPlan pl = lset_lists_plan(n, ls->nrows, G);
         lp->work_bytes = pl.work_bytes;
         lp->bound = pl.pairs;  // one per row and key
         lp->sizer = "lsmb_lset_lists_work_bytes";
-        lp->launch = [](lsmb_lset* ls, const KeyBatch& kb, uint64_t* d_starts, uint32_t* d_index, uint64_t cap,
-                        void* d_work, uint64_t work_bytes, hipStream_t st) {
+        lp->launch = [](lsmb_lset* ls, const KeyBatch& kb, const uint32_t*, uint32_t*, uint64_t* d_starts,
+                        uint32_t* d_index, uint64_t cap, void* d_work, uint64_t work_bytes, hipStream_t st) {
             return launch_lset_lists(kb, ls->rows, ls->base[ls->nrows], d_starts, d_index, cap, d_work, work_bytes,
                                      ls->c->num_cus, st);
         };
@@ -913,8 +933,8 @@ static int lset_lists_desc(const lsmb_lset* ls, bool version, uint64_t n, const 
     lp->work_bytes = pl.work_bytes;
     lp->bound = pl.entries;  // one per L0 table, row and key
     lp->sizer = "lsmb_lset_version_lists_work_bytes";
-    lp->launch = [](lsmb_lset* ls, const KeyBatch& kb, uint64_t* d_starts, uint32_t* d_index, uint64_t cap,
-                    void* d_work, uint64_t work_bytes, hipStream_t st) {
+    lp->launch = [](lsmb_lset* ls, const KeyBatch& kb, const uint32_t*, uint32_t*, uint64_t* d_starts,
+                    uint32_t* d_index, uint64_t cap, void* d_work, uint64_t work_bytes, hipStream_t st) {
         return launch_lset_version_lists(kb, ls->rows, ls->base[ls->nrows], (const RangedFilter*)ls->l0_desc.p,
                                          (uint32_t)ls->l0.size(), ls->l0_rg, ls->l0_cl, d_starts, d_index, cap, d_work,
                                          work_bytes, ls->c->num_cus, st);
@@ -922,7 +942,8 @@ static int lset_lists_desc(const lsmb_lset* ls, bool version, uint64_t n, const 
     return LSMB_OK;
 }
 
-// The device entry path.  Nothing to probe (no key, or no table): the starts are cleared on the stream.
+// The device entry path.  Nothing to probe (no key, or no table): the starts are
+// cleared on the stream (and a walk's steps, when wanted, all answer "none").
 static int lset_lists_dev(lsmb_lset* ls, const LsetListsProbe& lp, const void* d_data, const void* d_offsets,
                           uint32_t key_len, uint64_t n, void* d_starts, void* d_index, uint64_t cap, void* d_work,
                           uint64_t work_bytes, void* stream) {
@@ -939,10 +960,11 @@ static int lset_lists_dev(lsmb_lset* ls, const LsetListsProbe& lp, const void* d
     const hipStream_t st = pick_stream(ls->c, stream);
     if (idle) {
         HIP_TRY(hipMemsetAsync(d_starts, 0, (lp.total + 1) * 8, st));
+        if (lp.step && n) HIP_TRY(hipMemsetAsync(lp.step, 0xFF, n * 4, st));
         return LSMB_OK;
     }
     KeyBatch kb{(const uint8_t*)d_data, (const uint64_t*)d_offsets, key_len, n};
-    HIP_TRY(lp.launch(ls, kb, (uint64_t*)d_starts, (uint32_t*)d_index, cap, d_work, work_bytes, st));
+    HIP_TRY(lp.launch(ls, kb, lp.from, lp.step, (uint64_t*)d_starts, (uint32_t*)d_index, cap, d_work, work_bytes, st));
     return LSMB_OK;
 }
 
@@ -951,19 +973,27 @@ static int lset_lists_host(lsmb_lset* ls, const LsetListsProbe& lp, const uint8_
                            uint32_t key_len, uint64_t n, uint64_t* starts, uint32_t* index, uint64_t cap) {
     if (n && host_keys_null(data, offsets, key_len, n)) return fail(LSMB_EINVAL, "null keys");
     memset(starts, 0, (lp.total + 1) * 8);
-    if (n == 0 || lp.total == 0) return LSMB_OK;
+    if (n == 0 || lp.total == 0) {
+        if (lp.step) std::fill(lp.step, lp.step + n, LSMB_LSET_NONE);
+        return LSMB_OK;
+    }
     lsmb_ctx* c = ls->c;
     DevGuard g(c->dev);
-    // the scratch, carved: workspace | starts | index
+    // the scratch, carved: workspace | starts | a walk's resume points, then (in place) its steps | index
     const uint64_t dcap = std::min<uint64_t>(cap, lp.bound);
     const uint64_t sbytes = ((lp.total + 1) * 8 + kLlAlign - 1) / kLlAlign * kLlAlign;
-    HIP_TRY(c->out.ensure(lp.work_bytes + sbytes + std::max<uint64_t>(dcap, 1) * 4));
+    const uint64_t fbytes = lp.from || lp.step ? (n * 4 + kLlAlign - 1) / kLlAlign * kLlAlign : 0;
+    HIP_TRY(c->out.ensure(lp.work_bytes + sbytes + fbytes + std::max<uint64_t>(dcap, 1) * 4));
     uint8_t* w = (uint8_t*)c->out.p;
     uint64_t* d_starts = (uint64_t*)(w + lp.work_bytes);
-    uint32_t* d_index = (uint32_t*)(w + lp.work_bytes + sbytes);
+    uint32_t* d_fs = (uint32_t*)(w + lp.work_bytes + sbytes);
+    uint32_t* d_index = (uint32_t*)(w + lp.work_bytes + sbytes + fbytes);
     KeyBatch kb;
     if (int rc = stage_host_keys(c, data, offsets, key_len, n, &kb)) return rc;
-    HIP_TRY(lp.launch(ls, kb, d_starts, d_index, dcap, w, lp.work_bytes, c->st));
+    if (lp.from) HIP_TRY(hipMemcpyAsync(d_fs, lp.from, n * 4, hipMemcpyHostToDevice, c->st));
+    HIP_TRY(lp.launch(ls, kb, lp.from ? d_fs : nullptr, lp.step ? d_fs : nullptr, d_starts, d_index, dcap, w,
+                      lp.work_bytes, c->st));
+    if (lp.step) HIP_TRY(hipMemcpyAsync(lp.step, d_fs, n * 4, hipMemcpyDeviceToHost, c->st));  // lists_to_host waits
     return lists_to_host(starts, d_starts, lp.total, index, d_index, dcap, c->st);
 }
 
@@ -971,14 +1001,14 @@ int lsmb_lset_probe_lists_dev(lsmb_lset* ls, const void* d_data, const void* d_o
                               void* d_starts, void* d_index, uint64_t cap, void* d_work, uint64_t work_bytes,
                               void* stream) {
     LsetListsProbe lp;
-    if (int rc = lset_lists_desc(ls, false, n, d_starts, d_index, cap, &lp)) return rc;
+    if (int rc = lset_lists_desc(ls, LsetLists::Rows, n, d_starts, d_index, cap, &lp)) return rc;
     return lset_lists_dev(ls, lp, d_data, d_offsets, key_len, n, d_starts, d_index, cap, d_work, work_bytes, stream);
 }
 
 int lsmb_lset_probe_lists(lsmb_lset* ls, const uint8_t* data, const uint64_t* offsets, uint32_t key_len, uint64_t n,
                           uint64_t* starts, uint32_t* index, uint64_t cap) {
     LsetListsProbe lp;
-    if (int rc = lset_lists_desc(ls, false, n, starts, index, cap, &lp)) return rc;
+    if (int rc = lset_lists_desc(ls, LsetLists::Rows, n, starts, index, cap, &lp)) return rc;
     return lset_lists_host(ls, lp, data, offsets, key_len, n, starts, index, cap);
 }
 
@@ -1012,14 +1042,97 @@ int lsmb_lset_probe_version_lists_dev(lsmb_lset* ls, const void* d_data, const v
                                       uint64_t n, void* d_starts, void* d_index, uint64_t cap, void* d_work,
                                       uint64_t work_bytes, void* stream) {
     LsetListsProbe lp;
-    if (int rc = lset_lists_desc(ls, true, n, d_starts, d_index, cap, &lp)) return rc;
+    if (int rc = lset_lists_desc(ls, LsetLists::Version, n, d_starts, d_index, cap, &lp)) return rc;
     return lset_lists_dev(ls, lp, d_data, d_offsets, key_len, n, d_starts, d_index, cap, d_work, work_bytes, stream);
 }
 
 int lsmb_lset_probe_version_lists(lsmb_lset* ls, const uint8_t* data, const uint64_t* offsets, uint32_t key_len,
                                   uint64_t n, uint64_t* starts, uint32_t* index, uint64_t cap) {
     LsetListsProbe lp;
-    if (int rc = lset_lists_desc(ls, true, n, starts, index, cap, &lp)) return rc;
+    if (int rc = lset_lists_desc(ls, LsetLists::Version, n, starts, index, cap, &lp)) return rc;
+    return lset_lists_host(ls, lp, data, offsets, key_len, n, starts, index, cap);
+}
+
+// ------------------------------------------------- the walk's first candidate
+// DB::get and Snapshot::get stop at the first table that holds the key
+// (src/db/mod.rs:243-267, src/db/snapshot.rs:40-69).  Walk step w < T0 consults
+// the L0 table at position T0-1-w (version.level(0).iter().rev()), step T0 + r
+// row r; per key, the first step at or after its resume point whose table
+// passes src/sstable/reader.rs:192-199's check (lset_walk_plan.hpp).
+uint32_t lsmb_lset_walk_steps(const lsmb_lset* ls) {
+    return ls && ls->sealed ? lset_walk_steps((uint32_t)ls->l0.size(), ls->nrows) : 0;
+}
+
+// The per-key walk probe of kb on st (d_from and d_step may be null, or one buffer).
+static int lset_walk_launch(lsmb_lset* ls, const KeyBatch& kb, const uint32_t* d_from, uint32_t* d_step, uint32_t* d_ord,
+                            hipStream_t st) {
+    HIP_TRY(launch_lset_walk_first(kb, ls->rows, (const RangedFilter*)ls->l0_desc.p, (uint32_t)ls->l0.size(), ls->l0_rg,
+                                   ls->l0_cl, d_from, d_step, d_ord, ls->c->num_cus, st));
+    return LSMB_OK;
+}
+
+// What both per-key forms check before anything else.
+static int lset_walk_check(const lsmb_lset* ls, uint64_t n, const void* ord) {
+    if (int rc = lset_probe_check(ls)) return rc;
+    if (ls->l0.size() + ls->base[ls->nrows] >= UINT32_MAX)
+        return fail(LSMB_EINVAL, "more than 2^32-2 tables (0xFFFFFFFF is the 'no candidate' ordinal)");
+    if (n && !ord) return fail(LSMB_EINVAL, "null ord output");
+    return LSMB_OK;
+}
+
+int lsmb_lset_probe_walk_dev(lsmb_lset* ls, const void* d_data, const void* d_offsets, uint32_t key_len, uint64_t n,
+                             const void* d_from, void* d_step, void* d_ord, void* stream) {
+    if (int rc = lset_walk_check(ls, n, d_ord)) return rc;
+    if (n == 0) return LSMB_OK;
+    if (!d_data) return fail(LSMB_EINVAL, "null keys");
+    DevGuard g(ls->c->dev);
+    KeyBatch kb{(const uint8_t*)d_data, (const uint64_t*)d_offsets, key_len, n};
+    return lset_walk_launch(ls, kb, (const uint32_t*)d_from, (uint32_t*)d_step, (uint32_t*)d_ord,
+                            pick_stream(ls->c, stream));
+}
+
+int lsmb_lset_probe_walk(lsmb_lset* ls, const uint8_t* data, const uint64_t* offsets, uint32_t key_len, uint64_t n,
+                         const uint32_t* from, uint32_t* step, uint32_t* ord) {
+    if (int rc = lset_walk_check(ls, n, ord)) return rc;
+    if (n == 0) return LSMB_OK;
+    if (host_keys_null(data, offsets, key_len, n)) return fail(LSMB_EINVAL, "null keys");
+    lsmb_ctx* c = ls->c;
+    DevGuard g(c->dev);
+    // the context's output scratch: the resume points, then (in place) the steps | the ordinals
+    HIP_TRY(c->out.ensure(2 * n * 4));
+    uint32_t* d_fs = (uint32_t*)c->out.p;
+    uint32_t* d_ord = d_fs + n;
+    KeyBatch kb;
+    if (int rc = stage_host_keys(c, data, offsets, key_len, n, &kb)) return rc;
+    if (from) HIP_TRY(hipMemcpyAsync(d_fs, from, n * 4, hipMemcpyHostToDevice, c->st));
+    if (int rc = lset_walk_launch(ls, kb, from ? d_fs : nullptr, step ? d_fs : nullptr, d_ord, c->st)) return rc;
+    if (step) HIP_TRY(hipMemcpyAsync(step, d_fs, n * 4, hipMemcpyDeviceToHost, c->st));
+    HIP_TRY(hipMemcpyAsync(ord, d_ord, n * 4, hipMemcpyDeviceToHost, c->st));
+    HIP_TRY(hipStreamSynchronize(c->st));
+    return LSMB_OK;
+}
+
+uint64_t lsmb_lset_walk_lists_work_bytes(const lsmb_lset* ls, uint64_t n) {
+    if (!ls || !ls->sealed || n > UINT32_MAX) return 0;
+    return lset_walk_lists_plan(n, (uint64_t)ls->l0.size() + ls->base[ls->nrows]).work_bytes;
+}
+
+int lsmb_lset_probe_walk_lists_dev(lsmb_lset* ls, const void* d_data, const void* d_offsets, uint32_t key_len,
+                                   uint64_t n, const void* d_from, void* d_step, void* d_starts, void* d_index,
+                                   uint64_t cap, void* d_work, uint64_t work_bytes, void* stream) {
+    LsetListsProbe lp;
+    if (int rc = lset_lists_desc(ls, LsetLists::Walk, n, d_starts, d_index, cap, &lp)) return rc;
+    lp.from = (const uint32_t*)d_from;
+    lp.step = (uint32_t*)d_step;
+    return lset_lists_dev(ls, lp, d_data, d_offsets, key_len, n, d_starts, d_index, cap, d_work, work_bytes, stream);
+}
+
+int lsmb_lset_probe_walk_lists(lsmb_lset* ls, const uint8_t* data, const uint64_t* offsets, uint32_t key_len, uint64_t n,
+                               const uint32_t* from, uint32_t* step, uint64_t* starts, uint32_t* index, uint64_t cap) {
+    LsetListsProbe lp;
+    if (int rc = lset_lists_desc(ls, LsetLists::Walk, n, starts, index, cap, &lp)) return rc;
+    lp.from = from;
+    lp.step = step;
     return lset_lists_host(ls, lp, data, offsets, key_len, n, starts, index, cap);
 }
 

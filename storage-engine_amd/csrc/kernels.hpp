@@ -271,6 +271,30 @@ hipError_t launch_lset_version_lists(const KeyBatch& kb, const LsetRows& rows, u
                                      uint32_t* d_index, uint64_t cap, void* d_work, uint64_t work_bytes, int num_cus,
                                      hipStream_t st);
 
+// The walk probe (lset_walk_first.hip; steps and ordinals in
+// lset_walk_plan.hpp): with W = nl0 + rows.nrows walk steps, d_step[i] = the
+// smallest step w >= d_from[i] at which key i has a candidate (step w < nl0:
+// bit nl0-1-w of launch_lset_version's mask; step nl0 + r: launch_lset_probe
+// answers a table in row r), d_ord[i] = that candidate's Version ordinal, both
+// kLsetNone when there is none or d_from[i] >= W (such a key is not hashed).
+// d_from null = all zero, d_step null = not wanted, and the two may be one
+// buffer.  nl0 == 0 is allowed (nothing staged, d_l0 / rg / cl unread), and
+// rows.nrows == 0.  Read-only, no scratch.
+hipError_t launch_lset_walk_first(const KeyBatch& kb, const LsetRows& rows, const RangedFilter* d_l0, uint32_t nl0,
+                                  const FsetRanges& rg, const FsetClasses& cl, const uint32_t* d_from, uint32_t* d_step,
+                                  uint32_t* d_ord, int num_cus, hipStream_t st);
+
+// The walk probe per table: d_index[d_starts[v] .. d_starts[v+1]) = the
+// ascending key indices whose d_ord is v, over the V = nl0 + G Version
+// ordinals; a key is in at most one list.  d_starts[V + 1] is always exact, the
+// entry at position p is stored iff p < cap.  All scratch is d_work (16-B
+// aligned, at least lset_walk_lists_plan(kb.n, V).work_bytes).  1 <= kb.n <=
+// 2^32-1, 1 <= V <= 2^32-1.  No host synchronisation.
+hipError_t launch_lset_walk_lists(const KeyBatch& kb, const LsetRows& rows, uint64_t G, const RangedFilter* d_l0,
+                                  uint32_t nl0, const FsetRanges& rg, const FsetClasses& cl, const uint32_t* d_from,
+                                  uint32_t* d_step, uint64_t* d_starts, uint32_t* d_index, uint64_t cap, void* d_work,
+                                  uint64_t work_bytes, int num_cus, hipStream_t st);
+
 // A kernel launch whose completion also completes `done` (when non-null):
 // hipExtLaunchKernelGGL tracks the event with the dispatch's own completion
 // signal, where hipEventRecord after the launch would put a marker packet in

@@ -2,7 +2,8 @@
 // internal), with the hash and the 16-byte prefix already in hand: the loop
 // of lset.hip's probes and of the fused Version probe (lset_version.hip).
 // Steps 1-4 are described at the top of lset.hip; csrc/lset_order.hpp states
-// steps 1-3 in plain C++ (lset_find).
+// steps 1-3 in plain C++ (lset_find).  lset_row_find is one row of it, for the
+// walk probe (lset_walk_first.hip).
 #pragma once
 
 #include "kernels.hpp"
@@ -74,6 +75,46 @@ __device__ __forceinline__ void lset_rows_walk(const H128& h, const Pfx16& kx, c
         out[(uint64_t)r * stride + i] = ans;
         base += m;
     }
+}
+
+// One row of that walk on its own, for the walk probe (lset_walk_first.hip),
+// which stops at a key's first hit: the place in R's sealed order of the one
+// table that answers the key, else kLsetNone.  A second statement of the loop
+// body above, not a factor of it: with the body called from lset_rows_walk the
+// existing kernels compile to other registers (VarLen ordinal form 95 -> 106
+// VGPRs), and they are to stay as they are.
+__device__ __forceinline__ uint32_t lset_row_find(const H128& h, const Pfx16& kx, const uint8_t* kp, uint64_t kl,
+                                                  const LsetRow& R) {
+    const uint32_t m = R.ntab;
+    uint32_t lo = 0;
+    for (uint32_t step = m ? 1u << (31 - __builtin_clz(m)) : 0u; step; step >>= 1) {
+        const uint32_t j = lo + step - 1;
+        if (j < m) {
+            const ulonglong2 q = R.hi_pfx[j];
+            if (q.x < kx.w0 || (q.x == kx.w0 && q.y < kx.w1)) lo += step;
+        }
+    }
+    while (lo < m) {
+        const ulonglong2 q = R.hi_pfx[lo];
+        if (q.x != kx.w0 || q.y != kx.w1) break;
+        const LsetTable& T = R.tab[lo];
+        if (bound_cmp(q.x, q.y, T.hi, T.hi_len, kx, kp, kl) >= 0) break;
+        lo++;
+    }
+    if (lo >= m) return kLsetNone;
+    const LsetTable& T = R.tab[lo];
+    if (bound_cmp(T.lo_w0, T.lo_w1, T.lo, T.lo_len, kx, kp, kl) > 0) return kLsetNone;
+    if (const uint32_t k = T.k) {
+        const Mod32 md = T.md;
+        const uint32_t* __restrict__ w = T.words32;
+        PosWalk pw(md, h.lo, h.hi);
+        for (uint32_t j = 0; j < k; j++) {
+            const uint32_t p = pw.pos();
+            if (!((w[p >> 5] >> (p & 31)) & 1u)) return kLsetNone;
+            pw.next(md);
+        }
+    }
+    return lo;
 }
 
 }  // namespace lsmb

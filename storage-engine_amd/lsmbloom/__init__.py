@@ -137,6 +137,14 @@ SIGNATURES = {
                                                          ctypes.c_uint64, vp, ctypes.c_uint64, vp]),
     "lsmb_lset_probe_version_lists": (ctypes.c_int, [vp, u8p, u64p, ctypes.c_uint32, ctypes.c_uint64, u64p, u32p,
                                                      ctypes.c_uint64]),
+    "lsmb_lset_walk_steps": (ctypes.c_uint32, [vp]),
+    "lsmb_lset_probe_walk_dev": (ctypes.c_int, [vp, vp, vp, ctypes.c_uint32, ctypes.c_uint64, vp, vp, vp, vp]),
+    "lsmb_lset_probe_walk": (ctypes.c_int, [vp, u8p, u64p, ctypes.c_uint32, ctypes.c_uint64, u32p, u32p, u32p]),
+    "lsmb_lset_walk_lists_work_bytes": (ctypes.c_uint64, [vp, ctypes.c_uint64]),
+    "lsmb_lset_probe_walk_lists_dev": (ctypes.c_int, [vp, vp, vp, ctypes.c_uint32, ctypes.c_uint64, vp, vp, vp, vp,
+                                                      ctypes.c_uint64, vp, ctypes.c_uint64, vp]),
+    "lsmb_lset_probe_walk_lists": (ctypes.c_int, [vp, u8p, u64p, ctypes.c_uint32, ctypes.c_uint64, u32p, u32p, u64p,
+                                                  u32p, ctypes.c_uint64]),
     "lsmb_build_strategy": (ctypes.c_char_p, [ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint64]),
     "lsmb_host_max_keys": (ctypes.c_uint64, []),
     "lsmb_build_sweeps": (ctypes.c_int, [ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint64]),
@@ -1070,6 +1078,95 @@ class LevelSet:
         not written."""
         self._lists_dev(lib().lsmb_lset_probe_version_lists_dev, data, n, starts, index, work, offsets, key_len,
                         stream)
+
+    def walk_steps(self):
+        """W = l0_tables() + rows() (0 before seal): the steps of DB::get's
+        walk.  Step w < l0_tables() consults the L0 table at position
+        l0_tables() - 1 - w (step 0 the newest), step l0_tables() + r row r."""
+        return int(lib().lsmb_lset_walk_steps(self.h))
+
+    @staticmethod
+    def _resume(resume, n):
+        """A walk's resume steps (None: all zero) -> contiguous uint32[n] or None."""
+        if resume is None:
+            return None
+        resume = np.ascontiguousarray(resume, dtype=np.uint32)
+        if resume.shape != (n,):
+            raise ValueError("resume: one step per key")
+        return resume
+
+    def probe_walk(self, data, offsets=None, key_len=0, resume=None):
+        """Packed host keys (as probe) -> (step uint32[n], ord uint32[n]) from
+        one hash per key (lsmb_lset_probe_walk): step[i] = the first walk step
+        w >= resume[i] (None: 0) at which key i has a candidate (a set bit of
+        probe_version()'s mask, or a table answered by probe() in that row),
+        ord[i] that table's Version ordinal (version_order()); LSMB_LSET_NONE
+        in both when there is none or resume[i] >= walk_steps()."""
+        data, n, op = _host_keys(data, offsets, key_len)
+        resume = self._resume(resume, n)
+        step = np.empty(max(n, 1), dtype=np.uint32)
+        ord_ = np.empty(max(n, 1), dtype=np.uint32)
+        _check(lib().lsmb_lset_probe_walk(self.h, _p(data, u8p), op, key_len, n,
+                                          _p(resume, u32p) if resume is not None and n else None, _p(step, u32p),
+                                          _p(ord_, u32p)))
+        return step[:n], ord_[:n]
+
+    def probe_walk_keys(self, keys, resume=None):
+        """list of bytes -> (step, ord) as probe_walk."""
+        data, offs = _pack_keys(keys)
+        return self.probe_walk(data, offs, resume=resume)
+
+    def probe_walk_dev(self, data, n, ord, step=None, resume=None, offsets=None, key_len=0, stream=None):
+        """Device keys -> device answers (lsmb_lset_probe_walk_dev): ord and
+        step (optional) int32 / uint32 tensors of n, resume (optional) a tensor
+        of n resume steps; step may be the resume tensor itself."""
+        offs = vp(offsets.data_ptr()) if offsets is not None else None
+        _check(lib().lsmb_lset_probe_walk_dev(self.h, vp(data.data_ptr()), offs, key_len, n,
+                                              vp(resume.data_ptr()) if resume is not None else None,
+                                              vp(step.data_ptr()) if step is not None else None,
+                                              vp(ord.data_ptr()) if ord is not None else None, Context._stream(stream)))
+
+    def walk_lists_work_bytes(self, n):
+        """Bytes of device workspace probe_walk_lists_dev needs for n keys."""
+        return int(lib().lsmb_lset_walk_lists_work_bytes(self.h, int(n)))
+
+    def probe_walk_lists(self, data, offsets=None, key_len=0, cap=None, resume=None):
+        """Packed host keys (as probe) -> (starts uint64[V + 1], index
+        uint32[min(total, cap)], step uint32[n]) over Version ordinals:
+        index[starts[v]:starts[v+1]] = the ascending indices of the keys whose
+        first candidate at or after resume[i] is table v, so a key is in at
+        most one list (lsmb_lset_probe_walk_lists); step as probe_walk's.
+        cap=None sizes index from a counting call."""
+        n = _host_keys(data, offsets, key_len)[1]
+        resume = self._resume(resume, n)
+        step = np.empty(max(n, 1), dtype=np.uint32)
+        fn = lib().lsmb_lset_probe_walk_lists
+
+        def walk(h, p_data, op, klen, m, p_starts, p_index, c):
+            return fn(h, p_data, op, klen, m, _p(resume, u32p) if resume is not None and m else None, _p(step, u32p),
+                      p_starts, p_index, c)
+
+        starts, index = self._lists(walk, self.version_tables(), data, offsets, key_len, cap)
+        return starts, index, step[:n]
+
+    def probe_walk_lists_keys(self, keys, resume=None):
+        """list of bytes -> (starts, index, step) as probe_walk_lists."""
+        data, offs = _pack_keys(keys)
+        return self.probe_walk_lists(data, offs, resume=resume)
+
+    def probe_walk_lists_dev(self, data, n, starts, index, work, step=None, resume=None, offsets=None, key_len=0,
+                             stream=None):
+        """Device keys -> device lists (lsmb_lset_probe_walk_lists_dev): starts,
+        index and work as probe_version_lists_dev's, work of at least
+        walk_lists_work_bytes(n) bytes; step (optional) and resume (optional)
+        as probe_walk_dev's."""
+        fn = lib().lsmb_lset_probe_walk_lists_dev
+
+        def walk(h, d_data, offs, klen, m, d_starts, d_index, cap, d_work, wb, st):
+            return fn(h, d_data, offs, klen, m, vp(resume.data_ptr()) if resume is not None else None,
+                      vp(step.data_ptr()) if step is not None else None, d_starts, d_index, cap, d_work, wb, st)
+
+        self._lists_dev(walk, data, n, starts, index, work, offsets, key_len, stream)
 
 
 def build_strategy(num_bits, n, k=7):
