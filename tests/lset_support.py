@@ -304,6 +304,98 @@ def low_bits(mask, t0):
     return mask if t0 == 64 else mask & np.uint64((1 << t0) - 1)
 
 
+# ------- Version lists and the walk's device forms (test_lset_version_lists.py,
+# test_lset_walk.py, test_lset_model.py)
+
+def version_lists_from(mask, ids, t0, order_ids):
+    """probe_version()'s (mask uint64[n], ids uint32[R, n]) + table_order()'s
+    ids (unique) -> (starts uint64[t0 + G + 1], index uint32[total]): the L0
+    lists by position, then lists_from_ids' behind them."""
+    mask = np.asarray(mask, dtype=np.uint64)
+    l0 = [np.nonzero((mask >> np.uint64(j)) & np.uint64(1))[0].astype(np.uint32) for j in range(t0)]
+    rs, ri = lists_from_ids(ids, order_ids)
+    l0_starts = np.zeros(t0, dtype=np.uint64)
+    if t0:
+        l0_starts[1:] = np.cumsum([x.size for x in l0[:-1]], dtype=np.uint64)
+    e0 = np.uint64(sum(x.size for x in l0))
+    return (np.concatenate([l0_starts, rs + e0]).astype(np.uint64),
+            np.concatenate(l0 + [ri]).astype(np.uint32))
+
+
+def dev_vlists(ls, dq, n, cap=None, key_len=16, offsets=None, stream=None, work=None):
+    """probe_version_lists_dev into fresh tensors: starts pre-filled with -1,
+    index (cap entries; None: sized by a counting call) with POISON.  Returns
+    (starts uint64, index uint32 [cap]) on the host, the whole index buffer."""
+    import torch
+
+    V = ls.version_tables()
+    dev = dq.device
+    if work is None:
+        work = torch.empty(max(ls.version_lists_work_bytes(n), 1), dtype=torch.uint8, device=dev)
+    starts = torch.full((V + 1,), -1, dtype=torch.int64, device=dev)
+    if cap is None:
+        torch.cuda.synchronize()
+        ls.probe_version_lists_dev(dq, n, starts, None, work, offsets=offsets, key_len=key_len, stream=stream)
+        torch.cuda.synchronize()
+        cap = int(starts[V].item())
+        starts.fill_(-1)
+    index = torch.full((max(cap, 1),), POISON - (1 << 32), dtype=torch.int32, device=dev)
+    torch.cuda.synchronize()
+    ls.probe_version_lists_dev(dq, n, starts, index[:cap] if cap else None, work, offsets=offsets, key_len=key_len,
+                               stream=stream)
+    torch.cuda.synchronize()
+    return starts.cpu().numpy().view(np.uint64), index.cpu().numpy().view(np.uint32)[:cap]
+
+
+def dev_walk(ls, dq, n, resume=None, key_len=16, offsets=None, stream=None, in_place=False, want_step=True):
+    """probe_walk_dev into POISON-filled tensors -> (step or None, ord) on the
+    host.  in_place: step is the resume tensor itself."""
+    import torch
+
+    dev = dq.device
+    d_res = torch.from_numpy(np.asarray(resume, np.uint32).view(np.int32).copy()).to(dev) if resume is not None else None
+    d_ord = torch.full((max(n, 1),), POISON - (1 << 32), dtype=torch.int32, device=dev)
+    if in_place:
+        d_step = d_res
+    else:
+        d_step = torch.full((max(n, 1),), POISON - (1 << 32), dtype=torch.int32, device=dev) if want_step else None
+    torch.cuda.synchronize()
+    ls.probe_walk_dev(dq, n, d_ord, step=d_step, resume=d_res, offsets=offsets, key_len=key_len, stream=stream)
+    torch.cuda.synchronize()
+    step = d_step.cpu().numpy().view(np.uint32)[:n] if d_step is not None else None
+    if d_res is not None and not in_place:
+        assert np.array_equal(d_res.cpu().numpy().view(np.uint32), np.asarray(resume, np.uint32))  # only read
+    return step, d_ord.cpu().numpy().view(np.uint32)[:n]
+
+
+def dev_walk_lists(ls, dq, n, cap=None, resume=None, key_len=16, offsets=None, stream=None, work=None, want_step=True):
+    """probe_walk_lists_dev into fresh tensors: starts pre-filled with -1, index
+    (cap entries; None: sized by a counting call) and step with POISON.  Returns
+    (starts uint64, index uint32 [cap], step uint32 [n] or None) on the host."""
+    import torch
+
+    V = ls.version_tables()
+    dev = dq.device
+    if work is None:
+        work = torch.empty(max(ls.walk_lists_work_bytes(n), 1), dtype=torch.uint8, device=dev)
+    d_res = torch.from_numpy(np.asarray(resume, np.uint32).view(np.int32).copy()).to(dev) if resume is not None else None
+    starts = torch.full((V + 1,), -1, dtype=torch.int64, device=dev)
+    kw = dict(resume=d_res, offsets=offsets, key_len=key_len, stream=stream)
+    if cap is None:
+        torch.cuda.synchronize()
+        ls.probe_walk_lists_dev(dq, n, starts, None, work, **kw)
+        torch.cuda.synchronize()
+        cap = int(starts[V].item())
+        starts.fill_(-1)
+    index = torch.full((max(cap, 1),), POISON - (1 << 32), dtype=torch.int32, device=dev)
+    step = torch.full((max(n, 1),), POISON - (1 << 32), dtype=torch.int32, device=dev) if want_step else None
+    torch.cuda.synchronize()
+    ls.probe_walk_lists_dev(dq, n, starts, index[:cap] if cap else None, work, step=step, **kw)
+    torch.cuda.synchronize()
+    return (starts.cpu().numpy().view(np.uint64), index.cpu().numpy().view(np.uint32)[:cap],
+            step.cpu().numpy().view(np.uint32)[:n] if want_step else None)
+
+
 # ------------------------------- Version edits (test_lset_versions.py)
 
 CHUNK = 4 << 20  # the arena's chunk (include/lsmbloom.h, DESIGN.md section 4.4)

@@ -8,7 +8,7 @@ position v, v >= T0 the rows' ordinal v - T0, and
 
 The expectation is the CPU oracle's answer (reference() of
 tests/test_lset_version.py) and the set's own probe_version (held against the
-oracle there), transposed by version_lists_from below; the pass-edge test takes
+oracle there), transposed by lset_support's version_lists_from; the pass-edge test takes
 it from a bisect over the ranges.  Every comparison covers all V + 1 starts and
 all entries.
 """
@@ -23,8 +23,9 @@ import pytest
 import keygen
 import lsmbloom
 from lsmbloom import LevelSet
-from lset_support import (POISON, add_tables, always_maybe, build_table, check_lists, cpp_bin, dev_lists, expected_ids,
-                          expected_mask, l0_tables, lists_from_ids, low_bits, queries, reference, row_tables)
+from lset_support import (POISON, add_tables, always_maybe, build_table, check_lists, cpp_bin, dev_lists, dev_vlists,
+                          expected_ids, expected_mask, l0_tables, lists_from_ids, low_bits, queries, reference, row_tables,
+                          version_lists_from)
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 PLAN_SRC = os.path.join(ROOT, "tests", "cpp", "lset_vlists_plan_test.cpp")
@@ -32,21 +33,6 @@ NONE = lsmbloom.LSMB_LSET_NONE
 L0 = lsmbloom.LSMB_LSET_ROW_L0
 EINVAL = lsmbloom.LSMB_EINVAL
 vp = ctypes.c_void_p
-
-
-def version_lists_from(mask, ids, t0, order_ids):
-    """probe_version()'s (mask uint64[n], ids uint32[R, n]) + table_order()'s
-    ids (unique) -> (starts uint64[t0 + G + 1], index uint32[total]): the L0
-    lists by position, then lists_from_ids' behind them."""
-    mask = np.asarray(mask, dtype=np.uint64)
-    l0 = [np.nonzero((mask >> np.uint64(j)) & np.uint64(1))[0].astype(np.uint32) for j in range(t0)]
-    rs, ri = lists_from_ids(ids, order_ids)
-    l0_starts = np.zeros(t0, dtype=np.uint64)
-    if t0:
-        l0_starts[1:] = np.cumsum([x.size for x in l0[:-1]], dtype=np.uint64)
-    e0 = np.uint64(sum(x.size for x in l0))
-    return (np.concatenate([l0_starts, rs + e0]).astype(np.uint64),
-            np.concatenate(l0 + [ri]).astype(np.uint32))
 
 
 def own_lists(ls, mask, ids):
@@ -130,31 +116,6 @@ def ctx():
     c = lsmbloom.Context(0)
     yield c
     c.close()
-
-
-def dev_vlists(ls, dq, n, cap=None, key_len=16, offsets=None, stream=None, work=None):
-    """probe_version_lists_dev into fresh tensors: starts pre-filled with -1,
-    index (cap entries; None: sized by a counting call) with POISON.  Returns
-    (starts uint64, index uint32 [cap]) on the host, the whole index buffer."""
-    import torch
-
-    V = ls.version_tables()
-    dev = dq.device
-    if work is None:
-        work = torch.empty(max(ls.version_lists_work_bytes(n), 1), dtype=torch.uint8, device=dev)
-    starts = torch.full((V + 1,), -1, dtype=torch.int64, device=dev)
-    if cap is None:
-        torch.cuda.synchronize()
-        ls.probe_version_lists_dev(dq, n, starts, None, work, offsets=offsets, key_len=key_len, stream=stream)
-        torch.cuda.synchronize()
-        cap = int(starts[V].item())
-        starts.fill_(-1)
-    index = torch.full((max(cap, 1),), POISON - (1 << 32), dtype=torch.int32, device=dev)
-    torch.cuda.synchronize()
-    ls.probe_version_lists_dev(dq, n, starts, index[:cap] if cap else None, work, offsets=offsets, key_len=key_len,
-                               stream=stream)
-    torch.cuda.synchronize()
-    return starts.cpu().numpy().view(np.uint64), index.cpu().numpy().view(np.uint32)[:cap]
 
 
 def host_vlists(ls, kind, q):

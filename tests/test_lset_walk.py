@@ -23,8 +23,8 @@ import pytest
 import keygen
 import lsmbloom
 from lsmbloom import LevelSet
-from lset_support import (POISON, add_tables, always_maybe, build_table, check_lists, cpp_bin, expected_ids,
-                          expected_mask, l0_tables, low_bits, queries, reference, row_tables)
+from lset_support import (POISON, add_tables, always_maybe, build_table, check_lists, cpp_bin, dev_walk, dev_walk_lists,
+                          expected_ids, expected_mask, l0_tables, low_bits, queries, reference, row_tables)
 from walk_support import lists_from_ord, ordinals_of, walk_from
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -261,55 +261,6 @@ def test_walk_rounds_visit_every_candidate_once(ctx, oracle, kind):
         got = np.sort(np.concatenate(seen[v])) if seen[v] else np.zeros(0, np.uint32)
         assert np.array_equal(got, full[1][int(full[0][v]):int(full[0][v + 1])]), v
     ls.close()
-
-
-def dev_walk(ls, dq, n, resume=None, key_len=16, offsets=None, stream=None, in_place=False, want_step=True):
-    """probe_walk_dev into POISON-filled tensors -> (step or None, ord) on the
-    host.  in_place: step is the resume tensor itself."""
-    import torch
-
-    dev = dq.device
-    d_res = torch.from_numpy(np.asarray(resume, np.uint32).view(np.int32).copy()).to(dev) if resume is not None else None
-    d_ord = torch.full((max(n, 1),), POISON - (1 << 32), dtype=torch.int32, device=dev)
-    if in_place:
-        d_step = d_res
-    else:
-        d_step = torch.full((max(n, 1),), POISON - (1 << 32), dtype=torch.int32, device=dev) if want_step else None
-    torch.cuda.synchronize()
-    ls.probe_walk_dev(dq, n, d_ord, step=d_step, resume=d_res, offsets=offsets, key_len=key_len, stream=stream)
-    torch.cuda.synchronize()
-    step = d_step.cpu().numpy().view(np.uint32)[:n] if d_step is not None else None
-    if d_res is not None and not in_place:
-        assert np.array_equal(d_res.cpu().numpy().view(np.uint32), np.asarray(resume, np.uint32))  # only read
-    return step, d_ord.cpu().numpy().view(np.uint32)[:n]
-
-
-def dev_walk_lists(ls, dq, n, cap=None, resume=None, key_len=16, offsets=None, stream=None, work=None, want_step=True):
-    """probe_walk_lists_dev into fresh tensors: starts pre-filled with -1, index
-    (cap entries; None: sized by a counting call) and step with POISON.  Returns
-    (starts uint64, index uint32 [cap], step uint32 [n] or None) on the host."""
-    import torch
-
-    V = ls.version_tables()
-    dev = dq.device
-    if work is None:
-        work = torch.empty(max(ls.walk_lists_work_bytes(n), 1), dtype=torch.uint8, device=dev)
-    d_res = torch.from_numpy(np.asarray(resume, np.uint32).view(np.int32).copy()).to(dev) if resume is not None else None
-    starts = torch.full((V + 1,), -1, dtype=torch.int64, device=dev)
-    kw = dict(resume=d_res, offsets=offsets, key_len=key_len, stream=stream)
-    if cap is None:
-        torch.cuda.synchronize()
-        ls.probe_walk_lists_dev(dq, n, starts, None, work, **kw)
-        torch.cuda.synchronize()
-        cap = int(starts[V].item())
-        starts.fill_(-1)
-    index = torch.full((max(cap, 1),), POISON - (1 << 32), dtype=torch.int32, device=dev)
-    step = torch.full((max(n, 1),), POISON - (1 << 32), dtype=torch.int32, device=dev) if want_step else None
-    torch.cuda.synchronize()
-    ls.probe_walk_lists_dev(dq, n, starts, index[:cap] if cap else None, work, step=step, **kw)
-    torch.cuda.synchronize()
-    return (starts.cpu().numpy().view(np.uint64), index.cpu().numpy().view(np.uint32)[:cap],
-            step.cpu().numpy().view(np.uint32)[:n] if want_step else None)
 
 
 @pytest.fixture(scope="module")
