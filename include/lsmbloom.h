@@ -63,6 +63,22 @@ const char* lsmb_last_error(void);
 int lsmb_params(uint64_t expected_items, double false_positive_rate, uint32_t* num_bits,
                 uint32_t* num_hashes);
 
+/* The false-positive rate a filter's FILL predicts, (set_bits / num_bits)^num_hashes: the chance
+ * that may_contain finds all num_hashes positions of an absent key set.  The sizing above
+ * (src/bloom/mod.rs:38-68) aims the fill at 1/2 for expected_items keys; SSTableBuilder passes an
+ * ESTIMATE there (src/sstable/builder.rs:74), and a table that holds several times the estimate has
+ * a fill near 1 and answers true to nearly everything.  set_bits comes from lsmb_lset_census or
+ * lsmb_popcount_segs_dev.  num_hashes == 0 gives 1.0 (may_contain is then always true), also with
+ * num_bits == 0; set_bits > num_bits gives NaN, as does num_bits == 0 with num_hashes > 0.  Pure
+ * host arithmetic in doubles. */
+double lsmb_fill_fpr(uint32_t num_bits, uint32_t num_hashes, uint64_t set_bits);
+
+/* The number of DISTINCT keys a filter of that fill holds, -(m/k) * ln(1 - X/m) with m = num_bits,
+ * k = num_hashes, X = set_bits: the quantity to set against the estimated_keys the filter was sized
+ * for (src/sstable/builder.rs:74, through src/bloom/mod.rs:38-68).  X == m gives +inf (the filter
+ * is full: no count can be told), X == 0 gives 0; num_hashes == 0 and set_bits > num_bits give NaN. */
+double lsmb_fill_keys(uint32_t num_bits, uint32_t num_hashes, uint64_t set_bits);
+
 /* ceil(num_bits / 64): length of the words array (src/bloom/mod.rs:58). */
 uint64_t lsmb_num_words(uint32_t num_bits);
 
@@ -328,6 +344,18 @@ int lsmb_crc32_seg_dev(lsmb_ctx* ctx, const void* d_segs, uint64_t nseg, void* d
  * host synchronisation inside; nseg == 0 is LSMB_OK.  LSMB_EINVAL: NULL ctx, NULL d_segs with
  * nseg > 0.  This is what lsmb_lset_derive_packed moves its tables with. */
 int lsmb_copy_segs_dev(lsmb_ctx* ctx, const void* d_segs, uint64_t nseg, void* stream);
+/* The set bits of many small device segments in one launch (the filters of a resident Version,
+ * each sized from an estimate, src/sstable/builder.rs:74, by src/bloom/mod.rs:38-68): d_segs is
+ * nseg pairs {const void* words; uint64_t nbits} in device memory, words 16-byte aligned;
+ * d_out[s] (uint64_t, device memory) = the number of set bits among bits 0 .. nbits-1 of the LE u64
+ * words at `words`.  Exactly ceil(nbits / 64) 8-byte words are read, so the buffer may end with the
+ * last of them; bits at or above nbits in that word do not count (BloomFilter::deserialize never
+ * checks them, src/bloom/mod.rs:123-168, and may_contain never reads them); nbits == 0 answers 0
+ * and reads nothing.  One wave per segment; cut a long filter into several segments to spread it
+ * and add their counts.  Asynchronous on `stream` (NULL: the context's), no host synchronisation
+ * inside; nseg == 0 is LSMB_OK.  LSMB_EINVAL: NULL ctx, NULL d_segs or d_out with nseg > 0.  This
+ * is what lsmb_lset_census counts with. */
+int lsmb_popcount_segs_dev(lsmb_ctx* ctx, const void* d_segs, uint64_t nseg, void* d_out, void* stream);
 int lsmb_build_block_crc(lsmb_ctx* ctx, const uint8_t* data, const uint64_t* offsets, uint32_t key_len, uint64_t n,
                          uint32_t num_bits, uint32_t num_hashes, uint8_t* block, uint64_t block_len, uint32_t* crc);
 
@@ -844,6 +872,36 @@ uint64_t lsmb_lset_version_tables(const lsmb_lset* ls);
  * src/sstable/reader.rs:192-199).  Either pointer may be NULL.  Before seal:
  * LSMB_EINVAL. */
 int lsmb_lset_version_order(const lsmb_lset* ls, uint32_t* ids, uint64_t* part_base);
+
+/* ---- a Version's fill census -------------------------------------------------- */
+/* How good the filters of a resident Version are.  SSTableBuilder sizes each table's filter from an
+ * ESTIMATE of its key count (src/sstable/builder.rs:74 -> BloomFilter::new, src/bloom/mod.rs:38-68),
+ * and a flush or compaction output that holds several times the estimate gets a filter that is
+ * mostly ones: every may_contain on it is true, every probe lists it as a candidate, and the reader
+ * pays a table lookup per key for nothing.  The words of a sealed set live only in its arena
+ * (tables of lsmb_lset_add_batch_dev never crossed the host), so this is where a store learns which
+ * tables to rewrite with another rate, without re-reading a bloom block from disk. */
+
+/* Host outputs, V = lsmb_lset_version_tables(ls) entries each, in lsmb_lset_version_order's order
+ * (the L0 tables by position, then the rows' tables by ordinal): every table's filter geometry as
+ * it was added (src/bloom/mod.rs:38-68).  Either pointer may be NULL.  LSMB_EINVAL: NULL or
+ * unsealed set. */
+int lsmb_lset_version_geometry(const lsmb_lset* ls, uint32_t* num_bits, uint32_t* num_hashes);
+
+/* set_bits[v] (host, V entries, the same order) = the set bits below num_bits of table v's resident
+ * words; stray ones at or above num_bits in the last word (src/bloom/mod.rs:123-168 lets them in)
+ * and the arena's padding do not count.  With lsmb_lset_version_geometry it gives
+ * lsmb_fill_fpr and lsmb_fill_keys per table, the latter to set against builder.rs:74's estimate.
+ * The call plans the tables' words into items of at most 64 KiB on the host, stages them in pinned
+ * memory, and makes one upload, ONE launch (lsmb_popcount_segs_dev's kernel), one copy back of the
+ * item counts and ONE synchronisation of `stream` (NULL: a stream of the set's own), then adds the
+ * counts up per table on the host.  The set's tables are only read: probes on other streams or
+ * threads need no ordering with it, and tables shared with a parent (lsmb_lset_derive) or moved by
+ * lsmb_lset_derive_packed count like uploaded ones; lsmb_lset_stats is unchanged by it.  The
+ * staging is the set's own, so one census of a set runs at a time.  The result is NOT cached: a
+ * sealed set is immutable, so a store calls this once per Version and keeps the answer.
+ * V == 0 is LSMB_OK.  LSMB_EINVAL: NULL or unsealed set, NULL set_bits with V > 0. */
+int lsmb_lset_census(lsmb_lset* ls, uint64_t* set_bits, void* stream);
 
 /* Bytes of device workspace a Version lists probe of n keys needs (the batched
  * walk of src/db/mod.rs:238-267 / src/db/snapshot.rs:40-69 under

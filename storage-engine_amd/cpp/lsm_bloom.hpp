@@ -498,6 +498,46 @@ class LevelSet {
         check(lsmb_lset_version_order(ls_, o.ids.data(), o.part_base.data()));
         return o;
     }
+    // Every table's filter geometry in version_order()'s order
+    // (lsmb_lset_version_geometry; src/bloom/mod.rs:38-68).
+    struct VersionGeometry {
+        std::vector<uint32_t> num_bits, num_hashes;  // version_tables() each
+    };
+    VersionGeometry version_geometry() const {
+        VersionGeometry g;
+        g.num_bits.resize(version_tables());
+        g.num_hashes.resize(version_tables());
+        check(lsmb_lset_version_geometry(ls_, g.num_bits.data(), g.num_hashes.data()));
+        return g;
+    }
+    // The fill of every table's resident filter (lsmb_lset_census: one launch
+    // on `stream`, one wait), in version_order()'s order: set_bits below
+    // num_bits, fpr = lsmb_fill_fpr (the false-positive rate the fill
+    // predicts), keys = lsmb_fill_keys (the distinct keys a filter of that
+    // fill holds, against src/sstable/builder.rs:74's estimate).  Not cached:
+    // a sealed set is immutable, so call it once per Version.
+    struct Census {
+        std::vector<uint32_t> ids, num_bits, num_hashes;
+        std::vector<uint64_t> set_bits;
+        std::vector<double> fpr, keys;
+    };
+    Census census(void* stream = nullptr) {
+        Census c;
+        c.ids = version_order().ids;
+        VersionGeometry g = version_geometry();
+        c.num_bits = std::move(g.num_bits);
+        c.num_hashes = std::move(g.num_hashes);
+        const size_t V = c.ids.size();
+        c.set_bits.assign(V, 0);
+        check(lsmb_lset_census(ls_, c.set_bits.data(), stream));
+        c.fpr.resize(V);
+        c.keys.resize(V);
+        for (size_t v = 0; v < V; v++) {
+            c.fpr[v] = lsmb_fill_fpr(c.num_bits[v], c.num_hashes[v], c.set_bits[v]);
+            c.keys[v] = lsmb_fill_keys(c.num_bits[v], c.num_hashes[v], c.set_bits[v]);
+        }
+        return c;
+    }
     // index[starts[v] .. starts[v+1]) = the ascending indices of the keys that
     // table v answers (bit v of probe_version()'s mask, or probe()'s answer in
     // its row), from one hash per key; starts has version_tables() + 1

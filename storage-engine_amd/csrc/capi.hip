@@ -224,6 +224,20 @@ int lsmb_params(uint64_t n, double fpr, uint32_t* num_bits, uint32_t* num_hashes
     return LSMB_OK;
 }
 
+// What a filter's fill says (BloomFilter::new sizes for fill 1/2 at expected_items, mod.rs:38-68;
+// SSTableBuilder hands it an estimate, src/sstable/builder.rs:74).
+double lsmb_fill_fpr(uint32_t num_bits, uint32_t num_hashes, uint64_t set_bits) {
+    if (set_bits > num_bits) return NAN;
+    if (num_hashes == 0) return 1.0;  // may_contain's loop is empty: always true (mod.rs:82-94)
+    return pow((double)set_bits / (double)num_bits, (double)num_hashes);
+}
+
+double lsmb_fill_keys(uint32_t num_bits, uint32_t num_hashes, uint64_t set_bits) {
+    if (set_bits > num_bits || num_hashes == 0) return NAN;
+    const double m = (double)num_bits;
+    return -(m / (double)num_hashes) * log(1.0 - (double)set_bits / m) + 0.0;  // + 0.0: an empty filter holds 0, not -0
+}
+
 uint64_t lsmb_num_words(uint32_t num_bits) { return nwords64(num_bits); }
 uint64_t lsmb_serialized_size(uint32_t num_bits) { return 12 + 8 * nwords64(num_bits); }
 

@@ -2,7 +2,7 @@
 // Host-side plumbing only; the placement of filters in the arena is planned in
 // lset_arena.hpp, a repacking derive in lset_repack.hpp; the kernels are in
 // lset.hip, lset_lists.hip, lset_version.hip, lset_version_lists.hip,
-// lset_walk_first.hip, lset_repack.hip and crc32.hip.  Every add stages, copies
+// lset_walk_first.hip, lset_repack.hip, lset_census.hip and crc32.hip.  Every add stages, copies
 // and commits through lset_stage / lset_commit (a repacking derive through
 // lset_commit_arena); the six lists entry points describe their flavour
 // (LsetListsProbe) and run one device path (lset_lists_dev) or one host path
@@ -24,6 +24,7 @@
 #include "lset_repack.hpp"
 #include "lset_vlists_plan.hpp"
 #include "lset_walk_plan.hpp"
+#include "popcount_seg.hpp"
 
 using namespace lsmb;
 
@@ -113,6 +114,13 @@ struct lsmb_lset {
     // order) and the first ordinal of every row, base[nrows] = all tables
     std::vector<uint32_t> ids;
     uint64_t base[kLsetMaxRows + 1] = {0};
+    // seal: the filter of every ordinal, where it lives in the arena
+    // (lsmb_lset_version_geometry, lsmb_lset_census)
+    struct Geom {
+        const uint32_t* words;
+        uint32_t num_bits, k;
+    };
+    std::vector<Geom> geom;
     // seal, the L0 part: the boundary points' bytes, FsetPoint[] then the
     // region masks, RangedFilter[] (descriptor j = position j), and what the
     // kernels take by value
@@ -767,7 +775,11 @@ int lsmb_lset_seal(lsmb_lset* ls) {
     }
     for (uint32_t r = ls->nrows; r <= kLsetMaxRows; r++) ls->base[r] = at;
     ls->ids.resize(d.size());
-    for (size_t g = 0; g < d.size(); g++) ls->ids[g] = d[g].id;
+    ls->geom.resize(d.size());
+    for (size_t g = 0; g < d.size(); g++) {
+        ls->ids[g] = d[g].id;
+        ls->geom[g] = lsmb_lset::Geom{d[g].words32, d[g].num_bits, d[g].k};
+    }
     ls->sealed = true;
     return LSMB_OK;
 }
@@ -1134,6 +1146,59 @@ int lsmb_lset_probe_walk_lists(lsmb_lset* ls, const uint8_t* data, const uint64_
     lp.from = from;
     lp.step = step;
     return lset_lists_host(ls, lp, data, offsets, key_len, n, starts, index, cap);
+}
+
+// ------------------------------------------------- the fill census of a Version
+// SSTableBuilder sizes a table's filter from an estimate of its keys
+// (src/sstable/builder.rs:74), so a sealed set may hold filters that are mostly
+// ones; their words live only in the arena.  The census counts every table's
+// set bits there, in Version ordinals.
+int lsmb_lset_version_geometry(const lsmb_lset* ls, uint32_t* num_bits, uint32_t* num_hashes) {
+    if (int rc = lset_probe_check(ls)) return rc;
+    const uint64_t T0 = ls->l0.size();
+    for (uint64_t j = 0; j < T0; j++) {
+        if (num_bits) num_bits[j] = ls->l0[j].num_bits;
+        if (num_hashes) num_hashes[j] = ls->l0[j].k;
+    }
+    for (size_t g = 0; g < ls->geom.size(); g++) {
+        if (num_bits) num_bits[T0 + g] = ls->geom[g].num_bits;
+        if (num_hashes) num_hashes[T0 + g] = ls->geom[g].k;
+    }
+    return LSMB_OK;
+}
+
+// The items (popcount_seg.hpp) cross through the set's pinned staging, idle
+// since its last add; their counts come back next to them.
+int lsmb_lset_census(lsmb_lset* ls, uint64_t* set_bits, void* stream) {
+    if (int rc = lset_probe_check(ls)) return rc;
+    const uint64_t T0 = ls->l0.size(), V = T0 + ls->geom.size();
+    if (V == 0) return LSMB_OK;
+    if (!set_bits) return fail(LSMB_EINVAL, "null output");
+    std::vector<const void*> words(V);
+    std::vector<uint64_t> nbits(V);
+    for (uint64_t j = 0; j < T0; j++) words[j] = ls->l0[j].words, nbits[j] = ls->l0[j].num_bits;
+    for (size_t g = 0; g < ls->geom.size(); g++) words[T0 + g] = ls->geom[g].words, nbits[T0 + g] = ls->geom[g].num_bits;
+    std::vector<PopSeg> items;
+    std::vector<uint32_t> table_of;
+    popcount_items(words.data(), nbits.data(), V, &items, &table_of);
+    const size_t nit = items.size();
+    if (nit == 0) {  // no table has a bit
+        std::fill(set_bits, set_bits + V, (uint64_t)0);
+        return LSMB_OK;
+    }
+    DevGuard g(ls->c->dev);
+    const hipStream_t st = stream ? (hipStream_t)stream : ls->ust;
+    const size_t ibytes = nit * sizeof(PopSeg), cbytes = nit * sizeof(uint64_t);
+    if (int rc = pinned_ensure(ls->pin_retired, &ls->pin, &ls->pin_cap, ibytes + cbytes, "level set")) return rc;
+    memcpy(ls->pin, items.data(), ibytes);
+    HIP_TRY(ls->segs.ensure(ibytes + cbytes));
+    uint8_t* ds = (uint8_t*)ls->segs.p;
+    HIP_TRY(hipMemcpyAsync(ds, ls->pin, ibytes, hipMemcpyHostToDevice, st));
+    if (int rc = popcount_segs_dev((const PopSeg*)ds, nit, (uint64_t*)(ds + ibytes), st)) return rc;
+    HIP_TRY(hipMemcpyAsync(ls->pin + ibytes, ds + ibytes, cbytes, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));  // the census' one wait
+    popcount_fold((const uint64_t*)(ls->pin + ibytes), table_of.data(), nit, V, set_bits);
+    return LSMB_OK;
 }
 
 }  // extern "C"

@@ -255,6 +255,11 @@ int crc32_seg_dev(const CrcSeg* d_segs, uint64_t nseg, uint32_t* d_out, hipStrea
 // synchronised.
 struct CopySeg;
 int copy_segs_dev(const CopySeg* d_segs, uint64_t nseg, hipStream_t st);
+// The set bits of every segment (words, bits) of d_segs into d_out, both in
+// device memory: one launch of k_popcount_segs (lset_census.hip) on st,
+// nothing synchronised.
+struct PopSeg;
+int popcount_segs_dev(const PopSeg* d_segs, uint64_t nseg, uint64_t* d_out, hipStream_t st);
 uint32_t crc32_host(const uint8_t* p, uint64_t len, uint32_t crc);
 uint32_t crc32_combine_host(uint32_t crc_a, uint32_t crc_b, uint64_t len_b);
 

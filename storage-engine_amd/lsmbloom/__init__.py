@@ -46,6 +46,8 @@ SIGNATURES = {
     "lsmb_abi_version": (ctypes.c_int, []),
     "lsmb_last_error": (ctypes.c_char_p, []),
     "lsmb_params": (ctypes.c_int, [ctypes.c_uint64, ctypes.c_double, u32p, u32p]),
+    "lsmb_fill_fpr": (ctypes.c_double, [ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint64]),
+    "lsmb_fill_keys": (ctypes.c_double, [ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint64]),
     "lsmb_num_words": (ctypes.c_uint64, [ctypes.c_uint32]),
     "lsmb_serialized_size": (ctypes.c_uint64, [ctypes.c_uint32]),
     "lsmb_serialize": (ctypes.c_int, [u64p, ctypes.c_uint32, ctypes.c_uint32, u8p, ctypes.c_uint64]),
@@ -69,6 +71,7 @@ SIGNATURES = {
     "lsmb_crc32_dev": (ctypes.c_int, [vp, ctypes.c_uint32, vp, ctypes.c_uint64, u32p, vp]),
     "lsmb_crc32_seg_dev": (ctypes.c_int, [vp, vp, ctypes.c_uint64, vp, vp]),
     "lsmb_copy_segs_dev": (ctypes.c_int, [vp, vp, ctypes.c_uint64, vp]),
+    "lsmb_popcount_segs_dev": (ctypes.c_int, [vp, vp, ctypes.c_uint64, vp, vp]),
     "lsmb_fset_add_crc": (ctypes.c_int, [vp, u8p, ctypes.c_uint64, ctypes.c_uint32, u8p, ctypes.c_uint64, u8p,
                                          ctypes.c_uint64]),
     "lsmb_probe": (ctypes.c_int, [vp, ctypes.POINTER(u64p), u32p, u32p, ctypes.c_uint32, u8p, u64p,
@@ -132,6 +135,8 @@ SIGNATURES = {
     "lsmb_lset_probe_version": (ctypes.c_int, [vp, u8p, u64p, ctypes.c_uint32, ctypes.c_uint64, u64p, u32p]),
     "lsmb_lset_version_tables": (ctypes.c_uint64, [vp]),
     "lsmb_lset_version_order": (ctypes.c_int, [vp, u32p, u64p]),
+    "lsmb_lset_version_geometry": (ctypes.c_int, [vp, u32p, u32p]),
+    "lsmb_lset_census": (ctypes.c_int, [vp, u64p, vp]),
     "lsmb_lset_version_lists_work_bytes": (ctypes.c_uint64, [vp, ctypes.c_uint64]),
     "lsmb_lset_probe_version_lists_dev": (ctypes.c_int, [vp, vp, vp, ctypes.c_uint32, ctypes.c_uint64, vp, vp,
                                                          ctypes.c_uint64, vp, ctypes.c_uint64, vp]),
@@ -294,6 +299,16 @@ def params(expected_items, false_positive_rate):
     return nb.value, k.value
 
 
+def fill_fpr(num_bits, num_hashes, set_bits):
+    """(set_bits / num_bits) ** num_hashes, the false-positive rate a filter's fill predicts (lsmb_fill_fpr)."""
+    return float(lib().lsmb_fill_fpr(int(num_bits), int(num_hashes), int(set_bits)))
+
+
+def fill_keys(num_bits, num_hashes, set_bits):
+    """-(m / k) ln(1 - X / m), the distinct keys a filter of that fill holds (lsmb_fill_keys)."""
+    return float(lib().lsmb_fill_keys(int(num_bits), int(num_hashes), int(set_bits)))
+
+
 def ipc_export(t):
     """(handle bytes, byte offset) of the device allocation holding tensor t's
     storage (lsmb_ipc_export), for another process's Context.ipc_import."""
@@ -405,6 +420,16 @@ class Context:
         pointer, byte length) triples, pointers 16-byte aligned, lengths
         multiples of 16, ranges disjoint; asynchronous on stream."""
         _check(lib().lsmb_copy_segs_dev(self.h, vp(segs.data_ptr()), int(nseg), self._stream(stream)))
+
+    def popcount_segs_dev(self, segs, nseg, out, stream=None):
+        """The set bits of nseg device segments in one launch
+        (lsmb_popcount_segs_dev): segs an int64 / uint64 device tensor of
+        (words pointer, bit count) pairs, pointers 16-byte aligned, out an
+        int64 / uint64 device tensor of nseg; bits at or above a segment's bit
+        count do not count, and nothing past its last word is read;
+        asynchronous on stream."""
+        _check(lib().lsmb_popcount_segs_dev(self.h, vp(segs.data_ptr()), int(nseg), vp(out.data_ptr()),
+                                            self._stream(stream)))
 
     def probe(self, filters, data, offsets=None, key_len=0):
         """filters: [(words uint64 array, num_bits, k)] -> uint8 [n, ceil(F/8)] mask."""
@@ -1049,6 +1074,35 @@ class LevelSet:
         base = np.zeros(self.rows() + 2, dtype=np.uint64)
         _check(lib().lsmb_lset_version_order(self.h, _p(ids, u32p), _p(base, u64p)))
         return ids[:self.version_tables()], base
+
+    def version_geometry(self):
+        """-> (num_bits uint32[V], num_hashes uint32[V]): every table's filter
+        geometry in version_order()'s order (lsmb_lset_version_geometry)."""
+        V = self.version_tables()
+        nb = np.zeros(max(V, 1), dtype=np.uint32)
+        kk = np.zeros(max(V, 1), dtype=np.uint32)
+        _check(lib().lsmb_lset_version_geometry(self.h, _p(nb, u32p), _p(kk, u32p)))
+        return nb[:V], kk[:V]
+
+    def census(self, stream=None):
+        """The fill of every table's resident filter (lsmb_lset_census: one
+        launch on stream, one wait) -> (ids uint32[V], num_bits uint32[V],
+        num_hashes uint32[V], set_bits uint64[V], fpr float64[V], keys
+        float64[V]) in version_order()'s order: fpr the false-positive rate
+        the fill predicts (fill_fpr), keys the distinct keys a filter of that
+        fill holds (fill_keys), to set against the estimate the table's
+        filter was sized for.  Not cached: a sealed set is immutable, so call
+        it once per Version."""
+        ids, _ = self.version_order()
+        nb, kk = self.version_geometry()
+        V = ids.size
+        sb = np.zeros(max(V, 1), dtype=np.uint64)
+        _check(lib().lsmb_lset_census(self.h, _p(sb, u64p), Context._stream(stream)))
+        sb = sb[:V]
+        L = lib()
+        fpr = np.array([L.lsmb_fill_fpr(int(m), int(k), int(x)) for m, k, x in zip(nb, kk, sb)], dtype=np.float64)
+        keys = np.array([L.lsmb_fill_keys(int(m), int(k), int(x)) for m, k, x in zip(nb, kk, sb)], dtype=np.float64)
+        return ids, nb, kk, sb, fpr, keys
 
     def version_lists_work_bytes(self, n):
         """Bytes of device workspace probe_version_lists_dev needs for n keys."""
