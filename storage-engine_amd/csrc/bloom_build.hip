@@ -885,12 +885,9 @@ template <class Src>
 hipError_t launch_lds(const Src& src, const Launch& L) {
     const size_t smem = (size_t)L.nw32 * 4;
     // ~8 Ki keys per workgroup keeps the final per-word OR cheap.
-    uint64_t g = (L.n + 8191) / 8192;
-    const uint64_t gmax = (uint64_t)L.num_cus * (smem <= 40 * 1024 ? 4 : 1);
-    if (g > gmax) g = gmax;
-    if (g < 1) g = 1;
+    const uint32_t g = grid_for(L.n, 8192, (uint64_t)L.num_cus * (smem <= 40 * 1024 ? 4 : 1));
     set_max_lds((const void*)k_build_lds<Src>);
-    k_build_lds<Src><<<dim3((uint32_t)g), dim3(1024), smem, L.st>>>(src, L.n, L.md, L.k, L.nw32, L.gw);
+    k_build_lds<Src><<<dim3(g), dim3(1024), smem, L.st>>>(src, L.n, L.md, L.k, L.nw32, L.gw);
     L.record_t1();
     return L.record_done();
 }
@@ -920,9 +917,8 @@ hipError_t launch_tiled(const Src& src, const Launch& L) {
 
 template <class Src>
 hipError_t launch_atomic(const Src& src, const Launch& L) {
-    uint64_t g = (L.n + 255) / 256;
-    if (g > (uint64_t)L.num_cus * 8) g = (uint64_t)L.num_cus * 8;
-    k_build_atomic<Src><<<dim3((uint32_t)g), dim3(256), 0, L.st>>>(src, L.n, L.md, L.k, L.gw);
+    k_build_atomic<Src><<<dim3(grid_for(L.n, 256, (uint64_t)L.num_cus * 8)), dim3(256), 0, L.st>>>(src, L.n, L.md, L.k,
+                                                                                                  L.gw);
     L.record_t1();
     return L.record_done();
 }
@@ -1071,14 +1067,6 @@ hipError_t hash_records(const KeyBatch& kb, const Launch& L) {
     return launch_hash(FixedN{kb.data, kb.key_len}, L.n, rec, L.st);
 }
 
-// f(key source of kb)
-template <class F>
-hipError_t with_keys(const KeyBatch& kb, bool aligned16, F&& f) {
-    if (kb.offsets) return f(VarLen{kb.data, kb.offsets});
-    if (aligned16) return f(Fixed16{reinterpret_cast<const uint4*>(kb.data)});
-    return f(FixedN{kb.data, kb.key_len});
-}
-
 }  // namespace
 
 hipError_t launch_build(const KeyBatch& kb, uint32_t num_bits, uint32_t k, uint32_t* gw,
@@ -1095,7 +1083,7 @@ hipError_t launch_build(const KeyBatch& kb, uint32_t num_bits, uint32_t k, uint3
     }
     // every strategy but Partition has one sweep
     if (sweep > 0 && s != BuildStrategy::Partition) return L.record_done();
-    const bool aligned16 = !kb.offsets && kb.key_len == 16 && (reinterpret_cast<uintptr_t>(kb.data) & 15) == 0;
+    const bool aligned16 = ks::is_fixed16(kb);
     if (s == BuildStrategy::Partition) L.pl = plan_partition(num_bits, k, kb.n, num_cus);
     if (s == BuildStrategy::Tiled) L.tp = plan_tiled(num_bits, kb.n, num_cus);
     WorkspaceBytes need = workspace_bytes(s, L.pl, L.tp, num_bits, k, kb.n, aligned16, fresh);
@@ -1110,9 +1098,9 @@ hipError_t launch_build(const KeyBatch& kb, uint32_t num_bits, uint32_t k, uint3
     }
     hipError_t e;
     switch (s) {
-        case BuildStrategy::Lds: e = with_keys(kb, aligned16, [&](auto src) { return launch_lds(src, L); }); break;
-        case BuildStrategy::Tiled: e = with_keys(kb, aligned16, [&](auto src) { return launch_tiled(src, L); }); break;
-        case BuildStrategy::Atomic: e = with_keys(kb, aligned16, [&](auto src) { return launch_atomic(src, L); }); break;
+        case BuildStrategy::Lds: e = with_key_source(kb, [&](auto src) { return launch_lds(src, L); }); break;
+        case BuildStrategy::Tiled: e = with_key_source(kb, [&](auto src) { return launch_tiled(src, L); }); break;
+        case BuildStrategy::Atomic: e = with_key_source(kb, [&](auto src) { return launch_atomic(src, L); }); break;
         default:  // Partition
             if (aligned16) {
                 e = launch_partition(Fixed16{reinterpret_cast<const uint4*>(kb.data)}, L, sweep, fresh);
@@ -1132,25 +1120,19 @@ hipError_t launch_build(const KeyBatch& kb, uint32_t num_bits, uint32_t k, uint3
 
 hipError_t launch_or_reduce(uint32_t* dst, const uint32_t* src, uint64_t nw32, uint32_t nsrc,
                             uint64_t stride32, hipStream_t st, hipEvent_t done) {
-    uint64_t g = (nw32 + 255) / 256;
-    if (g > 8192) g = 8192;
-    if (g < 1) g = 1;
-    return launch_done(k_or_reduce, dim3((uint32_t)g), dim3(256), 0u, st, done, dst, src, nw32, nsrc, stride32);
+    return launch_done(k_or_reduce, dim3(grid_for(nw32, 256, 8192)), dim3(256), 0u, st, done, dst, src, nw32, nsrc,
+                       stride32);
 }
 
 hipError_t launch_gen_key16(uint64_t seed, uint64_t first, uint64_t n, uint8_t* d_keys, hipStream_t st) {
-    uint64_t g = (n + 255) / 256;
-    if (g > 8192) g = 8192;
-    if (g < 1) g = 1;
-    k_gen_key16<<<dim3((uint32_t)g), dim3(256), 0, st>>>(seed, first, n, reinterpret_cast<uint4*>(d_keys));
+    k_gen_key16<<<dim3(grid_for(n, 256, 8192)), dim3(256), 0, st>>>(seed, first, n, reinterpret_cast<uint4*>(d_keys));
     return hipGetLastError();
 }
 
 hipError_t launch_gen_splitmix(uint64_t seed, uint64_t first, uint64_t n, uint32_t mod, uint32_t add,
                                uint64_t* d_out, hipStream_t st) {
     if (n == 0) return hipSuccess;
-    const uint64_t g = std::min<uint64_t>((n + 255) / 256, 8192);
-    k_gen_splitmix<<<dim3((uint32_t)g), dim3(256), 0, st>>>(seed, first, n, mod, add, d_out);
+    k_gen_splitmix<<<dim3(grid_for(n, 256, 8192)), dim3(256), 0, st>>>(seed, first, n, mod, add, d_out);
     return hipGetLastError();
 }
 

@@ -196,6 +196,60 @@ struct Walk64 {
 // The 64-bit-safe walk, used where d may exceed 2^31.
 using PosWalk = Walk64;
 
+// BloomFilter::may_contain (src/bloom/mod.rs:82-94) over a filter's words in
+// memory (LE u32 view): the k positions of h walked in order, out at the first
+// clear bit (mod.rs:88-90).  k = 0 answers true.  Every probe that reads a
+// filter's own words calls this; the bit-sliced tables take table_and below.
+LSMB_HD bool words_may_contain(const uint32_t* __restrict__ words32, const Mod32 md, uint32_t k, const H128& h) {
+    bool hit = true;
+    if (k) {
+        PosWalk pw(md, h.lo, h.hi);
+        for (uint32_t j = 0; j < k; j++) {
+            const uint32_t p = pw.pos();
+            if (!((words32[p >> 5] >> (p & 31)) & 1u)) {
+                hit = false;
+                break;
+            }
+            pw.next(md);
+        }
+    }
+    return hit;
+}
+
+// The same test against a bit-sliced table (entry p = bit p of up to
+// 8*sizeof(T) filters that share (num_bits, k)): m ANDed with the entries at
+// the walk's k positions, all filters at once.  K > 0: k fixed at compile time,
+// unrolled, without the step past the last position; K = 0: the run-time k.
+template <int K, typename T, class W>
+LSMB_HD T table_and(const T* table, W pw, const typename W::Mod& md, uint32_t k, T m) {
+    if constexpr (K > 0) {
+#pragma unroll
+        for (int j = 0; j < K; j++) {
+            m &= table[pw.pos()];
+            if (j + 1 < K) pw.next(md);
+        }
+    } else {
+        for (uint32_t j = 0; j < k; j++) {
+            m &= table[pw.pos()];
+            pw.next(md);
+        }
+    }
+    return m;
+}
+
+// 8x8 bit transpose of a u64 read as 8 rows of 8 bits (row f = byte f): bit
+// 8 i + f of the result = bit 8 f + i of x.  Three masked delta swaps; the step
+// that turns 8 filters' bytes into 8 one-byte table entries (build_table8).
+LSMB_HD uint64_t transpose8x8(uint64_t x) {
+    uint64_t t = (x ^ (x >> 7)) & 0x00AA00AA00AA00AAull;
+    x ^= t ^ (t << 7);
+    t = (x ^ (x >> 14)) & 0x0000CCCC0000CCCCull;
+    x ^= t ^ (t << 14);
+    t = (x ^ (x >> 28)) & 0x00000000F0F0F0F0ull;
+    x ^= t ^ (t << 28);
+    return x;
+}
+
 // num_bits = 2^32 - 1: BloomFilter::new saturates `as u32` there
 // (src/bloom/mod.rs:49), so every filter sized for more than ~4.5e8 keys at
 // fpr 0.01 has it (C5's new(1e9, 0.01)).  2^32 = 1 (mod d): x mod d folds

@@ -156,27 +156,17 @@ __global__ __launch_bounds__(BS) void k_probe_sliced(Src src, uint64_t n, typena
         ob[f] = sf.ob[g];
         vm[f] = f < nfilt ? 1u : 0u;
     }
-    // One-byte entries with filter f on bit f (the probe's own layout): each
-    // (word, byte) item is an 8x8 bit transpose of the filters' bytes, three
-    // masked delta swaps on a u64, spread over all 1024 threads (a per-word
-    // loop of 32 x 8 bit extracts ran on 299 threads: ~900 VALU each).
+    // One-byte entries with filter f on bit f (the probe's own layout): the
+    // 8x8 bit transposes of build_table8 (fset_dev.hpp).
     bool ident = sizeof(T) == 1;
 #pragma unroll
     for (uint32_t f = 0; f < FMAX; f++) ident = ident && (f >= nfilt || ob[f] == f);  // absent slots: vm[f] = 0
-    if (ident) {
-        for (uint32_t it = threadIdx.x; it < 4 * nw32; it += blockDim.x) {
-            const uint32_t w = it >> 2, sh = 8 * (it & 3);
-            uint64_t x = 0;
+    if constexpr (sizeof(T) == 1) {
+        if (ident) {
+            uint32_t vm8[8];
 #pragma unroll
-            for (uint32_t f = 0; f < FMAX; f++) x |= (uint64_t)((wp[f][w] >> sh) & (0xFFu * vm[f])) << (8 * f);
-            // row f, column i (filter f's bit 8 (it&3) + i) -> row i, column f
-            uint64_t t = (x ^ (x >> 7)) & 0x00AA00AA00AA00AAull;
-            x ^= t ^ (t << 7);
-            t = (x ^ (x >> 14)) & 0x0000CCCC0000CCCCull;
-            x ^= t ^ (t << 14);
-            t = (x ^ (x >> 28)) & 0x00000000F0F0F0F0ull;
-            x ^= t ^ (t << 28);
-            *reinterpret_cast<uint64_t*>(reinterpret_cast<uint8_t*>(table) + 8 * it) = x;
+            for (uint32_t f = 0; f < 8; f++) vm8[f] = 0xFFu * vm[f];
+            build_table8(wp, vm8, nw32, smem_raw);
         }
     }
     for (uint32_t w = threadIdx.x; !ident && w < nw32; w += blockDim.x) {
@@ -200,13 +190,7 @@ __global__ __launch_bounds__(BS) void k_probe_sliced(Src src, uint64_t n, typena
     if constexpr (kRounds) {
         auto row = [&](const u32x4 v, uint32_t j) {
             const H128 h = xxh3_16(((uint64_t)v.y << 32) | v.x, ((uint64_t)v.w << 32) | v.z);
-            W pw(md, h.lo, h.hi);
-            T m = all;
-#pragma unroll
-            for (int jj = 0; jj < K; jj++) {
-                m &= table[pw.pos()];
-                if (jj + 1 < K) pw.next(md);
-            }
+            const T m = table_and<K>(table, W(md, h.lo, h.hi), md, k_, all);
             __builtin_amdgcn_raw_buffer_store_b8(m, R.rsrc(out, j, 1), R.lane, 0, 2 /* nt */);
         };
         for (uint32_t j = 0; j < R.rounds; j += kProbeDepth) {  // past the last round: empty windows (zeros, dropped rows)
@@ -227,21 +211,7 @@ __global__ __launch_bounds__(BS) void k_probe_sliced(Src src, uint64_t n, typena
         const typename Src::Pre cur = pre;
         pre = src.fetch(i + gs, i + gs < n);
         const H128 h = src.hash_pre(cur, i);
-        W pw(md, h.lo, h.hi);
-        T m = all;
-        if (K > 0) {
-#pragma unroll
-            for (int j = 0; j < K; j++) {
-                m &= table[pw.pos()];
-                if (j + 1 < K) pw.next(md);
-            }
-        } else {
-            for (uint32_t j = 0; j < k_; j++) {
-                m &= table[pw.pos()];
-                pw.next(md);
-            }
-        }
-        store_row<T>(out, i, stride, m);
+        store_row<T>(out, i, stride, table_and<K>(table, W(md, h.lo, h.hi), md, k_, all));
     }
 }
 
@@ -256,19 +226,7 @@ __global__ __launch_bounds__(256) void k_probe_generic(Src src, uint64_t n,
         uint64_t m = 0;
         for (uint32_t f = 0; f < nfilt; f++) {
             const ProbeFilter& F = filters[f];
-            bool hit = true;
-            if (F.k) {
-                PosWalk pw(F.md, h.lo, h.hi);
-                for (uint32_t j = 0; j < F.k; j++) {
-                    const uint32_t p = pw.pos();
-                    if (!((F.words32[p >> 5] >> (p & 31)) & 1u)) {
-                        hit = false;
-                        break;
-                    }
-                    pw.next(F.md);
-                }
-            }
-            if (hit) m |= 1ull << F.out_bit;
+            if (words_may_contain(F.words32, F.md, F.k, h)) m |= 1ull << F.out_bit;
         }
         for (uint32_t s = 0; s < stride; s++) out[i * stride + s] = (uint8_t)(m >> (8 * s));
     }
@@ -323,16 +281,8 @@ __global__ __launch_bounds__(256) void k_fset_probe(Src src, uint64_t n, const R
 #pragma unroll
                 for (uint32_t j = 0; j < 8; j++)
                     if (j < ck) hit = hit && ((R.f.words32[cpos[j] >> 5] >> (cpos[j] & 31)) & 1u);
-            } else if (R.f.k) {
-                PosWalk pw(R.f.md, h.lo, h.hi);
-                for (uint32_t j = 0; j < R.f.k; j++) {
-                    const uint32_t p = pw.pos();
-                    if (!((R.f.words32[p >> 5] >> (p & 31)) & 1u)) {
-                        hit = false;
-                        break;
-                    }
-                    pw.next(R.f.md);
-                }
+            } else {
+                hit = words_may_contain(R.f.words32, R.f.md, R.f.k, h);
             }
             if (hit) m |= 1ull << R.f.out_bit;
         }
@@ -375,19 +325,7 @@ __global__ __launch_bounds__(BS) void k_fset_sliced(Src src, uint64_t n, const R
             wp[f] = fl[f < nfilt ? f : 0].f.words32;
             vm[f] = f < nfilt ? 0xFFu : 0u;
         }
-        for (uint32_t it = threadIdx.x; it < 4 * nw32; it += blockDim.x) {
-            const uint32_t w = it >> 2, sh = 8 * (it & 3);
-            uint64_t x = 0;
-#pragma unroll
-            for (uint32_t f = 0; f < 8; f++) x |= (uint64_t)((wp[f][w] >> sh) & vm[f]) << (8 * f);
-            uint64_t t = (x ^ (x >> 7)) & 0x00AA00AA00AA00AAull;
-            x ^= t ^ (t << 7);
-            t = (x ^ (x >> 14)) & 0x0000CCCC0000CCCCull;
-            x ^= t ^ (t << 14);
-            t = (x ^ (x >> 28)) & 0x00000000F0F0F0F0ull;
-            x ^= t ^ (t << 28);
-            *reinterpret_cast<uint64_t*>(reinterpret_cast<uint8_t*>(table) + 8 * it) = x;
-        }
+        build_table8(wp, vm, nw32, smem_raw);
     }
     for (uint32_t w = threadIdx.x; sizeof(T) > 1 && w < nw32; w += blockDim.x) {
         T acc[32];
@@ -409,23 +347,9 @@ __global__ __launch_bounds__(BS) void k_fset_sliced(Src src, uint64_t n, const R
         const uint8_t* kp = src.bytes(i);
         const uint64_t kl = src.key_len(i);
         T m = (T)L.regmask[key_region(prefix16(kp, kl), kp, kl, L, npts)];
-        if (m) {
-            W pw(md, h.lo, h.hi);
-            if (K > 0) {
-#pragma unroll
-                for (int j = 0; j < K; j++) {
-                    m &= table[pw.pos()];
-                    if (j + 1 < K) pw.next(md);
-                }
-            } else {
-                for (uint32_t j = 0; j < k_; j++) {
-                    m &= table[pw.pos()];
-                    pw.next(md);
-                }
-            }
-        }
+        if (m) m = table_and<K>(table, W(md, h.lo, h.hi), md, k_, m);
         uint64_t o = (uint64_t)m;
-        if (!ident) {
+        if (!ident) {  // (k_fset_classes' ctz remap here instead costs the 1024-thread FixedN / VarLen forms a VGPR)
             o = 0;
             for (uint32_t f = 0; f < nfilt; f++)
                 if ((m >> f) & 1) o |= 1ull << fl[f].f.out_bit;
@@ -497,18 +421,13 @@ template <class Src>
 hipError_t fset_probe_with(const Src& src, uint64_t n, const RangedFilter* df, uint32_t nfilt, const FsetRanges& rg,
                            const FsetClasses& cl, uint32_t shared_nb, uint32_t shared_k, MaskOut out, int num_cus,
                            hipStream_t st, hipEvent_t done) {
-    uint64_t g = (n + 255) / 256;
-    const uint64_t gmax = (uint64_t)num_cus * 8;
-    if (g > gmax) g = gmax;
-    if (g < 1) g = 1;
+    const uint32_t g = grid_for(n, 256, (uint64_t)num_cus * 8);
     if (!(shared_nb > 0 && shared_k > 0) && cl.ncls > 0 && cl.table_bytes <= kFsetTableBytes) {
         const size_t smem = cl.table_bytes;
-        uint64_t gc = (n + kClassBlock - 1) / kClassBlock;
-        if (gc > (uint64_t)num_cus * class_wgs_per_cu<Src>()) gc = (uint64_t)num_cus * class_wgs_per_cu<Src>();
-        if (gc < 1) gc = 1;
+        const uint32_t gc = grid_for(n, kClassBlock, (uint64_t)num_cus * class_wgs_per_cu<Src>());
         hipFuncSetAttribute((const void*)k_fset_classes<Src>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
-        return launch_done(k_fset_classes<Src>, dim3((uint32_t)gc), dim3(kClassBlock), (uint32_t)smem, st, done, src, n, df,
-                           nfilt, rg, cl, out);
+        return launch_done(k_fset_classes<Src>, dim3(gc), dim3(kClassBlock), (uint32_t)smem, st, done, src, n, df, nfilt,
+                           rg, cl, out);
     }
     if (shared_nb > 0 && shared_k > 0) {
         const size_t tsz = nfilt <= 8 ? 1 : nfilt <= 16 ? 2 : nfilt <= 32 ? 4 : 8;
@@ -518,9 +437,9 @@ hipError_t fset_probe_with(const Src& src, uint64_t n, const RangedFilter* df, u
             auto go = [&](auto kern, auto md, uint32_t bs = 256) {
                 if (bs != 1024)  // (the 1024-thread kernels' table is static LDS)
                     hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
-                const uint64_t gb = bs == 256 ? g : std::min<uint64_t>((n + bs - 1) / bs, probe_wgs_per_cu(2) * num_cus);
-                return launch_done(kern, dim3((uint32_t)std::max<uint64_t>(gb, 1)), dim3(bs),
-                                   bs == 1024 ? 0u : (uint32_t)smem, st, done, src, n, df, nfilt, rg, shared_k, md, out);
+                const uint32_t gb = bs == 256 ? g : grid_for(n, bs, probe_wgs_per_cu(2) * num_cus);
+                return launch_done(kern, dim3(gb), dim3(bs), bs == 1024 ? 0u : (uint32_t)smem, st, done, src, n, df,
+                                   nfilt, rg, shared_k, md, out);
             };
             // (launch_done has consumed any launch error: return its result)
             if (tsz == 1) {
@@ -536,7 +455,7 @@ hipError_t fset_probe_with(const Src& src, uint64_t n, const RangedFilter* df, u
             return go(k_fset_sliced<Src, uint64_t, 0>, m32);
         }
     }
-    return launch_done(k_fset_probe<Src>, dim3((uint32_t)g), dim3(256), 0u, st, done, src, n, df, nfilt, rg, out);
+    return launch_done(k_fset_probe<Src>, dim3(g), dim3(256), 0u, st, done, src, n, df, nfilt, rg, out);
 }
 
 // Bytes of the bit-sliced LDS table the probe of these filters builds (all
@@ -555,10 +474,7 @@ template <class Src>
 hipError_t probe_with(const Src& src, uint64_t n, const ProbeFilter* hf, uint32_t nfilt,
                       const ProbeFilter* df, uint8_t* out, int num_cus, hipStream_t st, hipEvent_t done) {
     const uint32_t stride = (nfilt + 7) / 8;
-    uint64_t g = (n + 255) / 256;
-    const uint64_t gmax = (uint64_t)num_cus * 8;
-    if (g > gmax) g = gmax;
-    if (g < 1) g = 1;
+    const uint32_t g = grid_for(n, 256, (uint64_t)num_cus * 8);
     {
         const size_t smem = sliced_bytes(hf, nfilt);
         const uint32_t nb = hf[0].num_bits;
@@ -572,9 +488,8 @@ hipError_t probe_with(const Src& src, uint64_t n, const ProbeFilter* hf, uint32_
             auto go = [&](auto kern, auto md, uint32_t bs = 256) {
                 if (bs != 1024)  // (the 1024-thread kernels' table is static LDS)
                     hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
-                const uint64_t gb = bs == 256 ? g : std::min<uint64_t>((n + bs - 1) / bs, probe_wgs_per_cu(1) * num_cus);
-                kern<<<dim3((uint32_t)std::max<uint64_t>(gb, 1)), dim3(bs), bs == 1024 ? 0 : smem, st>>>(
-                    src, n, md, hf[0].k, nb, sf, nfilt, stride, out);
+                const uint32_t gb = bs == 256 ? g : grid_for(n, bs, probe_wgs_per_cu(1) * num_cus);
+                kern<<<dim3(gb), dim3(bs), bs == 1024 ? 0 : smem, st>>>(src, n, md, hf[0].k, nb, sf, nfilt, stride, out);
             };
             const Mod32 m32 = hf[0].md;
             // (the 1024-thread kernel counts its grid-wide rounds in 31 bits)
@@ -597,7 +512,7 @@ hipError_t probe_with(const Src& src, uint64_t n, const ProbeFilter* hf, uint32_
             return hipGetLastError();
         }
     }
-    return launch_done(k_probe_generic<Src>, dim3((uint32_t)g), dim3(256), 0u, st, done, src, n, df, nfilt, stride, out);
+    return launch_done(k_probe_generic<Src>, dim3(g), dim3(256), 0u, st, done, src, n, df, nfilt, stride, out);
 }
 
 }  // namespace
@@ -609,14 +524,9 @@ hipError_t launch_fset_probe(const KeyBatch& kb, const RangedFilter* df, uint32_
     if (nfilt > 64 || rg.npts > kFsetMaxPoints || cl.ncls > kFsetMaxClasses) return hipErrorInvalidValue;
     if (row_bytes != 1 && row_bytes != 2 && row_bytes != 4 && row_bytes != 8) return hipErrorInvalidValue;
     const MaskOut out{out_rows, row_bytes};
-    if (kb.offsets)
-        return fset_probe_with(VarLen{kb.data, kb.offsets}, kb.n, df, nfilt, rg, cl, shared_nb, shared_k, out, num_cus,
-                               st, done);
-    if (kb.key_len == 16 && (reinterpret_cast<uintptr_t>(kb.data) & 15) == 0)
-        return fset_probe_with(Fixed16{reinterpret_cast<const uint4*>(kb.data)}, kb.n, df, nfilt, rg, cl, shared_nb,
-                               shared_k, out, num_cus, st, done);
-    return fset_probe_with(FixedN{kb.data, kb.key_len}, kb.n, df, nfilt, rg, cl, shared_nb, shared_k, out, num_cus,
-                           st, done);
+    return with_key_source(kb, [&](auto src) {
+        return fset_probe_with(src, kb.n, df, nfilt, rg, cl, shared_nb, shared_k, out, num_cus, st, done);
+    });
 }
 
 bool probe_reads_descriptors(const ProbeFilter* hf, uint32_t nfilt) { return sliced_bytes(hf, nfilt) == 0; }
@@ -624,11 +534,7 @@ bool probe_reads_descriptors(const ProbeFilter* hf, uint32_t nfilt) { return sli
 hipError_t launch_probe(const KeyBatch& kb, const ProbeFilter* hf, uint32_t nfilt,
                         ProbeFilter* df, uint8_t* out, int num_cus, hipStream_t st, hipEvent_t done) {
     if (kb.n == 0) return hipSuccess;
-    if (kb.offsets) return probe_with(VarLen{kb.data, kb.offsets}, kb.n, hf, nfilt, df, out, num_cus, st, done);
-    if (kb.key_len == 16 && (reinterpret_cast<uintptr_t>(kb.data) & 15) == 0)
-        return probe_with(Fixed16{reinterpret_cast<const uint4*>(kb.data)}, kb.n, hf, nfilt, df, out,
-                          num_cus, st, done);
-    return probe_with(FixedN{kb.data, kb.key_len}, kb.n, hf, nfilt, df, out, num_cus, st, done);
+    return with_key_source(kb, [&](auto src) { return probe_with(src, kb.n, hf, nfilt, df, out, num_cus, st, done); });
 }
 
 }  // namespace lsmb

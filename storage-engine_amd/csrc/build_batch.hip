@@ -31,10 +31,6 @@ static_assert(kBbLdsBytes == kLdsBytes, "LDS per CU");
 static_assert(kBbMaxWords32 * 4 <= kBbLdsBytes, "a group item's image fits the LDS");
 static_assert((kBbWaveMaxBits / 32) * 4 * kBbWavesPerGroup <= kBbLdsBytes, "four wave regions fit the LDS");
 
-using ks::Fixed16;
-using ks::FixedN;
-using ks::VarLen;
-
 // Between an item's phases.  group: the workgroup's barrier.  wave: the 64
 // lanes run in lock step and the LDS serves one wave's operations in order,
 // so the compiler alone has to be kept from moving LDS accesses across.
@@ -141,14 +137,10 @@ hipError_t launch_build_batch(const KeyBatch& kb, const BbItem* d_items, uint32_
         return hipErrorInvalidValue;
     uint32_t* gw = reinterpret_cast<uint32_t*>(d_words);
     if (nwave + ngroup == 0) return done ? hipEventRecord(done, st) : hipSuccess;
-    if (kb.offsets)
-        return launch_classes(VarLen{kb.data, kb.offsets}, d_items, nzero, nwave, ngroup, wave_region32, group_region32,
-                              group_lanes, gw, st, done);
-    if (kb.key_len == 16 && (reinterpret_cast<uintptr_t>(kb.data) & 15) == 0)
-        return launch_classes(Fixed16{reinterpret_cast<const uint4*>(kb.data)}, d_items, nzero, nwave, ngroup,
-                              wave_region32, group_region32, group_lanes, gw, st, done);
-    return launch_classes(FixedN{kb.data, kb.key_len}, d_items, nzero, nwave, ngroup, wave_region32, group_region32,
-                          group_lanes, gw, st, done);
+    return with_key_source(kb, [&](auto src) {
+        return launch_classes(src, d_items, nzero, nwave, ngroup, wave_region32, group_region32, group_lanes, gw, st,
+                              done);
+    });
 }
 
 }  // namespace lsmb

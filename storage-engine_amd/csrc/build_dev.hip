@@ -9,6 +9,7 @@
 #include <type_traits>
 
 #include "ctx.hpp"
+#include "keysrc.hpp"
 
 namespace lsmb {
 
@@ -55,7 +56,7 @@ int take_workspace(lsmb_ctx* c, const WorkspaceBytes& need, hipStream_t st, Part
 int build_dev_ws(lsmb_ctx* c, const KeyBatch& kb_all, uint32_t num_bits, uint32_t k, uint32_t* dw, hipStream_t st,
                  BuildStrategy s, int sweep, bool fresh, hipEvent_t done = nullptr) {
     BuildTimers* tm = c->timing ? &c->tm : nullptr;
-    const bool aligned16 = !kb_all.offsets && kb_all.key_len == 16 && (reinterpret_cast<uintptr_t>(kb_all.data) & 15) == 0;
+    const bool aligned16 = ks::is_fixed16(kb_all);
     PartitionWorkspace ws;
     if (s != BuildStrategy::Partition) {  // one launch: Lds and Atomic builds take no workspace
         WorkspaceBytes need =

@@ -89,6 +89,24 @@ __device__ __forceinline__ void stage_classes(const RangedFilter* __restrict__ f
     for (uint32_t i = threadIdx.x; i < cl.ncls * 64; i += blockDim.x) S.mem[i / 64][i % 64] = cl.cls[i / 64].mem[i % 64];
 }
 
+// A one-byte bit-sliced table of up to 8 filters at `table` (LDS, 32 * nw32
+// bytes): entry p bit f = bit p of filter f's words wp[f], under the byte mask
+// vm[f] (0xFF, or 0 for an absent slot, whose wp re-reads a live filter).  Each
+// (word, byte) item is an 8x8 bit transpose of the filters' bytes, spread over
+// all threads of the workgroup (a per-word loop of 32 x 8 bit extracts ran on
+// 299 threads of 1024: ~900 VALU each).  A barrier must follow.
+__device__ __forceinline__ void build_table8(const uint32_t* const (&wp)[8], const uint32_t (&vm)[8], uint32_t nw32,
+                                             uint8_t* table) {
+    for (uint32_t it = threadIdx.x; it < 4 * nw32; it += blockDim.x) {
+        const uint32_t w = it >> 2, sh = 8 * (it & 3);
+        uint64_t x = 0;
+#pragma unroll
+        for (uint32_t f = 0; f < 8; f++) x |= (uint64_t)((wp[f][w] >> sh) & vm[f]) << (8 * f);
+        // row f, column i (filter f's bit 8 (it&3) + i) -> row i, column f
+        *reinterpret_cast<uint64_t*>(table + 8 * it) = transpose8x8(x);
+    }
+}
+
 // Class tables at `tables` (LDS, cl.table_bytes): thread w builds the 32
 // entries of word w, 32 members a pass.  A barrier must follow.
 __device__ __forceinline__ void build_class_tables(const FsetClasses& cl, const FsetClassLds& S, uint8_t* tables) {
@@ -96,7 +114,7 @@ __device__ __forceinline__ void build_class_tables(const FsetClasses& cl, const 
     for (uint32_t c = 0; c < cl.ncls; c++) {
         const uint32_t nw32 = (C[c].num_bits + 31) / 32, nm = C[c].nmem, width = C[c].width;
         uint8_t* t = tables + C[c].off;
-        if (width == 1) {  // (uniform) <= 8 members: 8x8 bit transposes over all threads, as k_fset_sliced
+        if (width == 1) {  // (uniform) <= 8 members: 8x8 bit transposes over all threads
             const uint32_t* wp[8];
             uint32_t vm[8];
 #pragma unroll
@@ -104,19 +122,7 @@ __device__ __forceinline__ void build_class_tables(const FsetClasses& cl, const 
                 wp[j] = S.fl[S.mem[c][j < nm ? j : 0]].f.words32;
                 vm[j] = j < nm ? 0xFFu : 0u;
             }
-            for (uint32_t it = threadIdx.x; it < 4 * nw32; it += blockDim.x) {
-                const uint32_t w = it >> 2, sh = 8 * (it & 3);
-                uint64_t x = 0;
-#pragma unroll
-                for (uint32_t j = 0; j < 8; j++) x |= (uint64_t)((wp[j][w] >> sh) & vm[j]) << (8 * j);
-                uint64_t q = (x ^ (x >> 7)) & 0x00AA00AA00AA00AAull;
-                x ^= q ^ (q << 7);
-                q = (x ^ (x >> 14)) & 0x0000CCCC0000CCCCull;
-                x ^= q ^ (q << 14);
-                q = (x ^ (x >> 28)) & 0x00000000F0F0F0F0ull;
-                x ^= q ^ (q << 28);
-                *reinterpret_cast<uint64_t*>(t + 8 * it) = x;
-            }
+            build_table8(wp, vm, nw32, t);
             continue;
         }
         for (uint32_t w = threadIdx.x; w < nw32; w += blockDim.x) {
@@ -169,18 +175,8 @@ __device__ __forceinline__ uint64_t classes_answer(const H128& h, uint64_t rm, c
         auto walk = [&](auto tag, auto pw, const auto& md) {
             using E = decltype(tag);
             const E* te = reinterpret_cast<const E*>(t);
-            if (kc == 7) {
-#pragma unroll
-                for (int j = 0; j < 7; j++) {
-                    acc &= te[pw.pos()];
-                    if (j < 6) pw.next(md);
-                }
-            } else {
-                for (uint32_t j = 0; j < kc; j++) {
-                    acc &= te[pw.pos()];
-                    pw.next(md);
-                }
-            }
+            if (kc == 7) acc = table_and<7>(te, pw, md, kc, (E)~(E)0);
+            else acc = table_and<0>(te, pw, md, kc, (E)~(E)0);
         };
         auto walk_w = [&](auto pw, const auto& md) {
             if (width == 1) walk(uint8_t{}, pw, md);
@@ -207,19 +203,7 @@ __device__ __forceinline__ uint64_t classes_answer(const H128& h, uint64_t rm, c
         const uint32_t f = (uint32_t)__builtin_ctzll(wm);
         wm &= wm - 1;
         const RangedFilter& R = S.fl[f];
-        bool hit = true;
-        if (R.f.k) {
-            PosWalk pw(R.f.md, h.lo, h.hi);
-            for (uint32_t j = 0; j < R.f.k; j++) {
-                const uint32_t p = pw.pos();
-                if (!((R.f.words32[p >> 5] >> (p & 31)) & 1u)) {
-                    hit = false;
-                    break;
-                }
-                pw.next(R.f.md);
-            }
-        }
-        if (hit) o |= 1ull << f;
+        if (words_may_contain(R.f.words32, R.f.md, R.f.k, h)) o |= 1ull << f;
     }
     return o & rm;
 }

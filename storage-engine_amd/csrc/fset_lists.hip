@@ -16,6 +16,7 @@
 // fset_lists_plan.hpp.
 #include "fset_lists_plan.hpp"
 #include "kernels.hpp"
+#include "wave.hpp"
 
 namespace lsmb {
 
@@ -26,10 +27,6 @@ constexpr int kListWaves = kListBlock / 64;
 constexpr int kListChunks = (int)kListTile / kListBlock;        // chunks (rows) per lane
 static_assert(kListTile % kListBlock == 0, "a tile is a whole number of chunks per wave");
 constexpr int kScanBlock = 1024;                                // 16 waves, one live slot each per round
-
-__device__ __forceinline__ uint32_t lane_id() {
-    return __builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u));
-}
 
 // The lane's rows of tile `tile`: row k is key tile * kListTile + (wave *
 // kListChunks + k) * 64 + lane; rows past n read as 0 (no bit set).
@@ -85,15 +82,6 @@ __global__ __launch_bounds__(kListBlock) void k_lists_count(const Row* __restric
     }
 }
 
-__device__ __forceinline__ uint32_t wave_incl_scan(uint32_t v, uint32_t lane) {
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-        const uint32_t up = __shfl_up(v, d);
-        if (lane >= (uint32_t)d) v += up;
-    }
-    return v;
-}
-
 // One workgroup.  Wave w takes the live slots j = w, w + 16, ...: it replaces
 // counts[j][0 .. ntiles) by their exclusive scan (each tile's offset inside the
 // slot's list, < 2^32 as n is) 256 tiles a step, and leaves the slot's total
@@ -130,12 +118,7 @@ __global__ __launch_bounds__(kScanBlock) void k_lists_scan(uint32_t* __restrict_
         const bool is_live = (live >> lane) & 1;
         const uint32_t j = (uint32_t)__popcll(live & ((1ull << lane) - 1));
         const uint64_t cnt = is_live ? total[j] : 0;
-        uint64_t v = cnt;
-#pragma unroll
-        for (int d = 1; d < 64; d <<= 1) {
-            const uint64_t up = __shfl_up(v, d);
-            if (lane >= (uint32_t)d) v += up;
-        }
+        const uint64_t v = wave_incl_scan(cnt, lane);
         starts[lane] = v - cnt;
         if (lane == 63) starts[64] = v;
     }

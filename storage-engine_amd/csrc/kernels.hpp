@@ -308,6 +308,15 @@ hipError_t launch_done(K kern, dim3 grid, dim3 block, uint32_t smem, hipStream_t
     return hipGetLastError();
 }
 
+// Workgroups for n grid-strided items at `block` items per workgroup (its
+// lanes, for most kernels): ceil(n / block) within [1, max_wgs] (max_wgs = the
+// device's CUs times the kernel's workgroups per CU).
+inline uint32_t grid_for(uint64_t n, uint32_t block, uint64_t max_wgs) {
+    uint64_t g = (n + block - 1) / block;
+    if (g > max_wgs) g = max_wgs;
+    return (uint32_t)(g < 1 ? 1 : g);
+}
+
 // True when launch_probe walks these filters with k_probe_generic, the one
 // probe kernel that reads the device descriptor copy (the bit-sliced kernels
 // take the filters in their arguments).

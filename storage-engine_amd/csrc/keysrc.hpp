@@ -2,6 +2,7 @@
 #pragma once
 
 #include "bloom_math.hpp"
+#include "kernels.hpp"
 
 namespace lsmb {
 
@@ -107,7 +108,22 @@ struct Recs {
     __device__ __forceinline__ WalkRec hash_pre(const Pre& v, uint64_t) const { return v; }
 };
 
+// 16-byte keys on a 16-byte-aligned base: the batches Fixed16 reads (and pass A
+// hashes inline).
+inline bool is_fixed16(const KeyBatch& kb) {
+    return !kb.offsets && kb.key_len == 16 && (reinterpret_cast<uintptr_t>(kb.data) & 15) == 0;
+}
+
 }  // namespace ks
+
+// The launchers' choice of key source: f(src) with the VarLen, Fixed16 or
+// FixedN view of the batch.
+template <class F>
+auto with_key_source(const KeyBatch& kb, F&& f) {
+    if (kb.offsets) return f(ks::VarLen{kb.data, kb.offsets});
+    if (ks::is_fixed16(kb)) return f(ks::Fixed16{reinterpret_cast<const uint4*>(kb.data)});
+    return f(ks::FixedN{kb.data, kb.key_len});
+}
 
 // Register pins (an empty asm consuming the value) for a walk seed.
 __device__ __forceinline__ void pin_seed(const H128& h) {

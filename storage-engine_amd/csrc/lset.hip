@@ -27,10 +27,6 @@
 namespace lsmb {
 namespace {
 
-using ks::Fixed16;
-using ks::FixedN;
-using ks::VarLen;
-
 // The walk of one key batch over every row, shared by both forms of the
 // answer: kOrdinal = false stores the hit's table id at out[r * n + i];
 // kOrdinal = true its ordinal (the tables of rows 0 .. r-1, then its place in
@@ -62,45 +58,33 @@ __global__ __launch_bounds__(256) void k_lset_probe_ord(Src src, uint64_t n, Lse
     lset_probe_body<Src, true>(src, n, rows, out, stride, gs);
 }
 
-template <class Src>
-hipError_t lset_probe_with(const Src& src, uint64_t n, const LsetRows& rows, uint32_t* out, int num_cus, hipStream_t st) {
-    uint64_t g = (n + 255) / 256;
-    const uint64_t gmax = (uint64_t)num_cus * 8;
-    if (g > gmax) g = gmax;
-    k_lset_probe<Src><<<dim3((uint32_t)g), dim3(256), 0, st>>>(src, n, rows, out);
-    return hipGetLastError();
-}
-
-template <class Src>
-hipError_t lset_probe_ord_with(const Src& src, uint64_t n, const LsetRows& rows, uint32_t* out, uint64_t stride,
-                               int num_cus, hipStream_t st) {
-    uint64_t g = (n + 255) / 256;
-    const uint64_t gmax = (uint64_t)num_cus * 8;
-    if (g > gmax) g = gmax;
-    k_lset_probe_ord<Src><<<dim3((uint32_t)g), dim3(256), 0, st>>>(src, n, rows, out, stride);
-    return hipGetLastError();
+// Both forms behind one host path: the grid, then the id kernel (rows n apart)
+// or the ordinal kernel (rows `stride` apart).
+template <bool kOrdinal>
+hipError_t lset_probe_any(const KeyBatch& kb, const LsetRows& rows, uint32_t* d_out, uint64_t stride, int num_cus,
+                          hipStream_t st) {
+    if (kb.n == 0 || rows.nrows == 0) return hipSuccess;
+    if (rows.nrows > kLsetMaxRows || (kOrdinal && stride < kb.n)) return hipErrorInvalidValue;
+    return with_key_source(kb, [&](auto src) {
+        using Src = decltype(src);
+        const dim3 g(grid_for(kb.n, 256, (uint64_t)num_cus * 8));
+        if constexpr (kOrdinal)
+            k_lset_probe_ord<Src><<<g, dim3(256), 0, st>>>(src, kb.n, rows, d_out, stride);
+        else
+            k_lset_probe<Src><<<g, dim3(256), 0, st>>>(src, kb.n, rows, d_out);
+        return hipGetLastError();
+    });
 }
 
 }  // namespace
 
 hipError_t launch_lset_probe(const KeyBatch& kb, const LsetRows& rows, uint32_t* d_out, int num_cus, hipStream_t st) {
-    if (kb.n == 0 || rows.nrows == 0) return hipSuccess;
-    if (rows.nrows > kLsetMaxRows) return hipErrorInvalidValue;
-    if (kb.offsets) return lset_probe_with(VarLen{kb.data, kb.offsets}, kb.n, rows, d_out, num_cus, st);
-    if (kb.key_len == 16 && (reinterpret_cast<uintptr_t>(kb.data) & 15) == 0)
-        return lset_probe_with(Fixed16{reinterpret_cast<const uint4*>(kb.data)}, kb.n, rows, d_out, num_cus, st);
-    return lset_probe_with(FixedN{kb.data, kb.key_len}, kb.n, rows, d_out, num_cus, st);
+    return lset_probe_any<false>(kb, rows, d_out, kb.n, num_cus, st);
 }
 
 hipError_t launch_lset_probe_ordinals(const KeyBatch& kb, const LsetRows& rows, uint32_t* d_out, uint64_t stride,
                                       int num_cus, hipStream_t st) {
-    if (kb.n == 0 || rows.nrows == 0) return hipSuccess;
-    if (rows.nrows > kLsetMaxRows || stride < kb.n) return hipErrorInvalidValue;
-    if (kb.offsets) return lset_probe_ord_with(VarLen{kb.data, kb.offsets}, kb.n, rows, d_out, stride, num_cus, st);
-    if (kb.key_len == 16 && (reinterpret_cast<uintptr_t>(kb.data) & 15) == 0)
-        return lset_probe_ord_with(Fixed16{reinterpret_cast<const uint4*>(kb.data)}, kb.n, rows, d_out, stride, num_cus,
-                                   st);
-    return lset_probe_ord_with(FixedN{kb.data, kb.key_len}, kb.n, rows, d_out, stride, num_cus, st);
+    return lset_probe_any<true>(kb, rows, d_out, stride, num_cus, st);
 }
 
 }  // namespace lsmb

@@ -31,6 +31,7 @@
 // for the bounds, read from device memory (null = 0, the rows' own probe).
 #include "kernels.hpp"
 #include "lset_lists_plan.hpp"
+#include "wave.hpp"
 
 namespace lsmb {
 
@@ -39,10 +40,6 @@ namespace {
 static_assert(kLlBlock == kLlDigits, "thread t of a workgroup owns digit t");
 static_assert(kLlNone == kLsetNone, "the plan header restates the probe's 'no table'");
 static_assert(kLlChunks * 64 <= (1u << 23), "packed (earlier + rank) field");
-
-__device__ __forceinline__ uint32_t ll_lane_id() {
-    return __builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u));
-}
 
 // What a pass reads.  First pass: the answer rows (element = row r, key i;
 // value = i; a miss is no element).  Later passes: the E pairs of the pass
@@ -64,7 +61,7 @@ template <bool kFirst>
 __device__ __forceinline__ void ll_tile_rank(const LlSrc& s, uint32_t tile, uint64_t count, uint32_t shift,
                                              uint32_t (&key)[kLlChunks], uint32_t (&val)[kLlChunks],
                                              uint32_t (&pk)[kLlChunks], uint32_t (*wcnt)[kLlDigits]) {
-    const uint32_t lane = ll_lane_id(), wave = threadIdx.x >> 6;
+    const uint32_t lane = lane_id(), wave = threadIdx.x >> 6;
 #pragma unroll
     for (uint32_t j = 0; j < kLlWaves; j++) (&wcnt[0][0])[threadIdx.x + j * kLlBlock] = 0;
     bool valid[kLlChunks];
@@ -164,12 +161,14 @@ __global__ __launch_bounds__(kLlBlock) void k_ll_rowscan(uint64_t* __restrict__ 
                                                          uint64_t* __restrict__ total_out) {
     __shared__ uint64_t part[kLlBlock];
     __shared__ uint64_t wtot[kLlWaves];
-    const uint32_t lane = ll_lane_id(), wave = threadIdx.x >> 6;
+    const uint32_t lane = lane_id(), wave = threadIdx.x >> 6;
     uint64_t carry = ll_block_sum(threadIdx.x < blockIdx.x ? totals[threadIdx.x] : 0, part);
     uint64_t* row = counts + (uint64_t)blockIdx.x * ntiles;
     for (uint32_t t0 = 0; t0 < ntiles; t0 += kLlBlock) {
         const uint32_t t = t0 + threadIdx.x;
         const uint64_t v = t < ntiles ? row[t] : 0;
+        // (wave_incl_scan written out: with the call this kernel compiles to other code, and the lists
+        // probe it belongs to measured 0.3 % slower, AB_LOG.md)
         uint64_t incl = v;
 #pragma unroll
         for (int d = 1; d < 64; d <<= 1) {
@@ -316,10 +315,8 @@ hipError_t launch_lset_lists_split(const LsetListsPlan& pl, void* d_work, const 
         s.vals = ov;
         sorted = ok;
     }
-    uint64_t g = (pl.pairs + 1 + 255) / 256;
-    const uint64_t gmax = (uint64_t)num_cus * 8;
-    if (g > gmax) g = gmax;
-    k_ll_bounds<<<dim3((uint32_t)g), dim3(256), 0, st>>>(sorted, count, G, d_starts, d_base, ord_off);
+    k_ll_bounds<<<dim3(grid_for(pl.pairs + 1, 256, (uint64_t)num_cus * 8)), dim3(256), 0, st>>>(sorted, count, G, d_starts,
+                                                                                             d_base, ord_off);
     return hipGetLastError();
 }
 

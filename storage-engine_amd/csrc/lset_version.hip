@@ -30,10 +30,6 @@
 namespace lsmb {
 namespace {
 
-using ks::Fixed16;
-using ks::FixedN;
-using ks::VarLen;
-
 // k_fset_classes' geometry (fset_dev.hpp): 1024-thread workgroups, two per CU
 // for 16-B keys, one for the other key sources, so a CU builds the class
 // tables at most twice.  The row search adds no register beyond that cap's 64
@@ -76,14 +72,12 @@ template <class Src, bool kOrdinal>
 hipError_t lset_version_with(const Src& src, uint64_t n, const LsetRows& rows, const RangedFilter* d_l0, uint32_t nl0,
                              const FsetRanges& rg, const FsetClasses& cl, uint8_t* d_mask, uint32_t rb, uint32_t* d_out,
                              uint64_t stride, int num_cus, hipStream_t st) {
-    uint64_t g = (n + kClassBlock - 1) / kClassBlock;
-    const uint64_t gmax = (uint64_t)num_cus * class_wgs_per_cu<Src>();
-    if (g > gmax) g = gmax;
+    const uint32_t g = grid_for(n, kClassBlock, (uint64_t)num_cus * class_wgs_per_cu<Src>());
     const size_t smem = cl.table_bytes;
     hipFuncSetAttribute((const void*)k_lset_version<Src, kOrdinal>, hipFuncAttributeMaxDynamicSharedMemorySize,
                         (int)smem);
-    k_lset_version<Src, kOrdinal><<<dim3((uint32_t)g), dim3(kClassBlock), smem, st>>>(src, n, rows, d_l0, nl0, rg, cl,
-                                                                                        d_mask, rb, d_out, stride);
+    k_lset_version<Src, kOrdinal><<<dim3(g), dim3(kClassBlock), smem, st>>>(src, n, rows, d_l0, nl0, rg, cl, d_mask, rb,
+                                                                              d_out, stride);
     return hipGetLastError();
 }
 
@@ -97,14 +91,10 @@ hipError_t lset_version_any(const KeyBatch& kb, const LsetRows& rows, const Rang
         cl.table_bytes > kFsetTableBytes)
         return hipErrorInvalidValue;
     if (!d_mask || (rows.nrows && !d_out)) return hipErrorInvalidValue;
-    if (kb.offsets)
-        return lset_version_with<VarLen, kOrdinal>(VarLen{kb.data, kb.offsets}, kb.n, rows, d_l0, nl0, rg, cl, d_mask,
-                                                   rb, d_out, stride, num_cus, st);
-    if (kb.key_len == 16 && (reinterpret_cast<uintptr_t>(kb.data) & 15) == 0)
-        return lset_version_with<Fixed16, kOrdinal>(Fixed16{reinterpret_cast<const uint4*>(kb.data)}, kb.n, rows, d_l0,
-                                                    nl0, rg, cl, d_mask, rb, d_out, stride, num_cus, st);
-    return lset_version_with<FixedN, kOrdinal>(FixedN{kb.data, kb.key_len}, kb.n, rows, d_l0, nl0, rg, cl, d_mask, rb,
-                                               d_out, stride, num_cus, st);
+    return with_key_source(kb, [&](auto src) {
+        return lset_version_with<decltype(src), kOrdinal>(src, kb.n, rows, d_l0, nl0, rg, cl, d_mask, rb, d_out, stride,
+                                                          num_cus, st);
+    });
 }
 
 }  // namespace

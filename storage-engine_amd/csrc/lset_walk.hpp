@@ -54,6 +54,7 @@ __device__ __forceinline__ void lset_rows_walk(const H128& h, const Pfx16& kx, c
         if (lo < m) {
             const LsetTable& T = R.tab[lo];
             if (bound_cmp(T.lo_w0, T.lo_w1, T.lo, T.lo_len, kx, kp, kl) <= 0) {
+                // words_may_contain, written out: called here, the lists probe measured 0.3 % slower (AB_LOG.md)
                 bool hit = true;
                 const uint32_t k = T.k;
                 if (k) {
@@ -79,10 +80,13 @@ __device__ __forceinline__ void lset_rows_walk(const H128& h, const Pfx16& kx, c
 
 // One row of that walk on its own, for the walk probe (lset_walk_first.hip),
 // which stops at a key's first hit: the place in R's sealed order of the one
-// table that answers the key, else kLsetNone.  A second statement of the loop
-// body above, not a factor of it: with the body called from lset_rows_walk the
-// existing kernels compile to other registers (VarLen ordinal form 95 -> 106
-// VGPRs), and they are to stay as they are.
+// table that answers the key, else kLsetNone.  The row search above the
+// filter walk is stated twice on purpose: as one function called from
+// lset_rows_walk it costs k_lset_version<VarLen, ordinal> 95 -> 106 VGPRs
+// (occupancy 5 -> 4) and the FixedN forms of k_lset_probe, k_lset_probe_ord
+// and k_lset_version two more SGPR spills each.  The filter walk is
+// words_may_contain here; lset_rows_walk writes the same loop out, where the
+// call moves no register but measured slower in the lists probe.
 __device__ __forceinline__ uint32_t lset_row_find(const H128& h, const Pfx16& kx, const uint8_t* kp, uint64_t kl,
                                                   const LsetRow& R) {
     const uint32_t m = R.ntab;
@@ -104,17 +108,7 @@ __device__ __forceinline__ uint32_t lset_row_find(const H128& h, const Pfx16& kx
     if (lo >= m) return kLsetNone;
     const LsetTable& T = R.tab[lo];
     if (bound_cmp(T.lo_w0, T.lo_w1, T.lo, T.lo_len, kx, kp, kl) > 0) return kLsetNone;
-    if (const uint32_t k = T.k) {
-        const Mod32 md = T.md;
-        const uint32_t* __restrict__ w = T.words32;
-        PosWalk pw(md, h.lo, h.hi);
-        for (uint32_t j = 0; j < k; j++) {
-            const uint32_t p = pw.pos();
-            if (!((w[p >> 5] >> (p & 31)) & 1u)) return kLsetNone;
-            pw.next(md);
-        }
-    }
-    return lo;
+    return words_may_contain(T.words32, T.md, T.k, h) ? lo : kLsetNone;
 }
 
 }  // namespace lsmb

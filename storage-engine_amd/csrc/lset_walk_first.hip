@@ -41,10 +41,6 @@
 namespace lsmb {
 namespace {
 
-using ks::Fixed16;
-using ks::FixedN;
-using ks::VarLen;
-
 static_assert(kWalkNone == kLsetNone, "the plan header restates the probe's 'no table'");
 
 // d_from (null: all zero) and d_step (null: not wanted) may be one buffer:
@@ -108,13 +104,11 @@ template <class Src>
 hipError_t lset_walk_with(const Src& src, uint64_t n, const LsetRows& rows, const RangedFilter* d_l0, uint32_t nl0,
                           const FsetRanges& rg, const FsetClasses& cl, const uint32_t* d_from, uint32_t* d_step,
                           uint32_t* d_ord, int num_cus, hipStream_t st) {
-    uint64_t g = (n + kClassBlock - 1) / kClassBlock;
-    const uint64_t gmax = (uint64_t)num_cus * class_wgs_per_cu<Src>();
-    if (g > gmax) g = gmax;
+    const uint32_t g = grid_for(n, kClassBlock, (uint64_t)num_cus * class_wgs_per_cu<Src>());
     const size_t smem = nl0 ? cl.table_bytes : 0;
     hipFuncSetAttribute((const void*)k_lset_walk_first<Src>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
-    k_lset_walk_first<Src><<<dim3((uint32_t)g), dim3(kClassBlock), smem, st>>>(src, n, rows, d_l0, nl0, rg, cl, d_from,
-                                                                              d_step, d_ord);
+    k_lset_walk_first<Src><<<dim3(g), dim3(kClassBlock), smem, st>>>(src, n, rows, d_l0, nl0, rg, cl, d_from, d_step,
+                                                                    d_ord);
     return hipGetLastError();
 }
 
@@ -127,13 +121,9 @@ hipError_t launch_lset_walk_first(const KeyBatch& kb, const LsetRows& rows, cons
     if (rows.nrows > kLsetMaxRows || nl0 > 64 || !d_ord) return hipErrorInvalidValue;
     if (nl0 && (!d_l0 || rg.npts > kFsetMaxPoints || cl.ncls > kFsetMaxClasses || cl.table_bytes > kFsetTableBytes))
         return hipErrorInvalidValue;
-    if (kb.offsets)
-        return lset_walk_with(VarLen{kb.data, kb.offsets}, kb.n, rows, d_l0, nl0, rg, cl, d_from, d_step, d_ord, num_cus,
-                              st);
-    if (kb.key_len == 16 && (reinterpret_cast<uintptr_t>(kb.data) & 15) == 0)
-        return lset_walk_with(Fixed16{reinterpret_cast<const uint4*>(kb.data)}, kb.n, rows, d_l0, nl0, rg, cl, d_from,
-                              d_step, d_ord, num_cus, st);
-    return lset_walk_with(FixedN{kb.data, kb.key_len}, kb.n, rows, d_l0, nl0, rg, cl, d_from, d_step, d_ord, num_cus, st);
+    return with_key_source(kb, [&](auto src) {
+        return lset_walk_with(src, kb.n, rows, d_l0, nl0, rg, cl, d_from, d_step, d_ord, num_cus, st);
+    });
 }
 
 hipError_t launch_lset_walk_lists(const KeyBatch& kb, const LsetRows& rows, uint64_t G, const RangedFilter* d_l0,

@@ -219,11 +219,9 @@ hipError_t launch_or_gather(uint64_t* dst, const OrSources& s, uint64_t nwords, 
     bool a16 = ((uintptr_t)dst & 15) == 0 && (nwords & 1) == 0;
     for (uint32_t j = 0; j < s.n; j++) a16 = a16 && ((uintptr_t)s.p[j] & 15) == 0;
     const uint64_t count = a16 ? nwords / 2 : nwords;
-    uint64_t g = (count + 255) / 256;
-    g = std::min<uint64_t>(g, (uint64_t)num_cus * 8);
-    if (g < 1) g = 1;
-    if (a16) return or_gather_n((uint4*)dst, s, count, (uint32_t)g, status, st);
-    return or_gather_n(dst, s, count, (uint32_t)g, status, st);
+    const uint32_t g = grid_for(count, 256, (uint64_t)num_cus * 8);
+    if (a16) return or_gather_n((uint4*)dst, s, count, g, status, st);
+    return or_gather_n(dst, s, count, g, status, st);
 }
 
 // dst words of slice r (slice_words each, nwords in all) from s.p[r] where set.
@@ -233,10 +231,7 @@ hipError_t launch_copy_slices(uint64_t* dst, const OrSources& s, uint64_t slice_
     bool a16 = ((uintptr_t)dst & 15) == 0 && (nwords & 1) == 0 && (slice_words & 1) == 0;
     for (uint32_t j = 0; j < s.n; j++) a16 = a16 && ((uintptr_t)s.p[j] & 15) == 0;
     const uint64_t per = a16 ? slice_words / 2 : slice_words, count = a16 ? nwords / 2 : nwords;
-    uint64_t gx = (per + 1023) / 1024;  // 256 threads x 4 elements per block
-    gx = std::min<uint64_t>(gx, std::max<uint64_t>(1, (uint64_t)num_cus * 8 / s.n));
-    if (gx < 1) gx = 1;
-    const dim3 grid((uint32_t)gx, s.n);
+    const dim3 grid(grid_for(per, 1024, (uint64_t)num_cus * 8 / s.n), s.n);  // 256 threads x 4 elements per block
     if (a16)
         k_copy_slices<uint4><<<grid, dim3(256), 0, st>>>((uint4*)dst, s, per, count, status);
     else
@@ -632,8 +627,8 @@ int lsmb_poison_fill_dev(lsmb_ctx* c, void* d_words, uint64_t nwords, const uint
     if (((uintptr_t)d_status & 3) != 0) return fail(LSMB_EINVAL, "d_status is not 4-byte aligned");
     DevGuard g(c->dev);
     // a small grid: when the merge is healthy every block only reads the status
-    const uint64_t blocks = std::max<uint64_t>(1, std::min<uint64_t>((nwords + 255) / 256, (uint64_t)c->num_cus));
-    k_poison_fill<<<dim3((uint32_t)blocks), dim3(256), 0, pick_stream(c, stream)>>>((uint64_t*)d_words, nwords, d_status);
+    k_poison_fill<<<dim3(grid_for(nwords, 256, (uint64_t)c->num_cus)), dim3(256), 0, pick_stream(c, stream)>>>(
+        (uint64_t*)d_words, nwords, d_status);
     HIP_TRY(hipGetLastError());
     return LSMB_OK;
 }

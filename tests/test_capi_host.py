@@ -306,6 +306,28 @@ def test_reductions_at_quotient_edges(tmp_path):
     assert ", 0 bad" in out.stdout
 
 
+@pytest.mark.parametrize("san", [[], ["-Xarch_host", "-fsanitize=address,undefined",
+                                      "-Xarch_host", "-fno-sanitize-recover=undefined"]], ids=["plain", "asan_ubsan"])
+def test_probe_steps_against_literal_restatements(tmp_path, san):
+    """The device steps the probe kernels share, on the host: words_may_contain
+    against a literal (h1 + i*h2 wrapping) % num_bits test of all k bits over
+    num_bits in {1, 63, 64, 65, 9 586, 2^20} x k in {0, 1, 7, 8, 33} (200
+    inserted keys all true, 2 000 other keys equal to the literal answer);
+    table_and<7> and table_and<0> over the table sliced from 8 such filters,
+    bit f = words_may_contain of filter f; transpose8x8 bit for bit and as an
+    involution (tests/cpp/probe_prims_test.cpp, host build of the device
+    header, plain and under the address and undefined-behaviour sanitizers)."""
+    import subprocess
+    exe = str(tmp_path / "probe_prims_test")
+    src = os.path.join(ROOT, "tests", "cpp", "probe_prims_test.cpp")
+    r = subprocess.run(["/opt/rocm/bin/hipcc", "-O2", "-std=c++17", "-Wall", "--offload-arch=gfx950", *san, src,
+                        "-o", exe], capture_output=True, text=True)
+    assert r.returncode == 0, r.stderr[-3000:]
+    out = subprocess.run([exe], capture_output=True, text=True, timeout=300)
+    assert out.returncode == 0, out.stdout + out.stderr
+    assert ", 0 bad" in out.stdout
+
+
 def test_missing_library_fails_loudly(tmp_path):
     """No HIP library, no product: the mirror raises instead of falling back
     to the oracle or any host path (fresh interpreter, library path pointed

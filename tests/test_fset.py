@@ -189,12 +189,14 @@ def test_fset_add_rejects_corrupt_blocks_like_deserialize(oracle):
 
 @pytest.mark.gpu
 @pytest.mark.parametrize("ntab,n,fpr", [(5, 800, 0.05), (12, 800, 0.01), (20, 800, 0.01), (33, 800, 0.001),
-                                        (40, 500, 0.01), (64, 500, 0.01)])
+                                        (40, 500, 0.01), (64, 500, 0.01), (33, 2000, 0.001)])
 def test_fset_same_sized_sliced_table_widths(oracle, ntab, n, fpr):
     # every filter of the set shares (num_bits, k): the bit-sliced LDS table
     # path at 8/16/32/64-bit entries (after removing slot 1: 4, 11, 19 / 32,
     # 39 and 63 filters; each table within 64 KiB of LDS) and k != 7, with a
-    # non-identity slot -> output-bit mapping (slot 1 is gone)
+    # non-identity slot -> output-bit mapping (slot 1 is gone).  The last case's
+    # table (32 filters of 28 702 bits, 4-byte entries) is past 64 KiB: its
+    # k = 10 filters are walked from L2 one by one (k_fset_probe above 8 hashes)
     ctx = lsmbloom.Context(0)
     fs = FilterSet(ctx)
     nb, k = lsmbloom.params(n, fpr)
