@@ -312,6 +312,76 @@ int lsmb_build_batch_blocks(lsmb_ctx* ctx, const uint8_t* data, const uint64_t* 
                             uint64_t ntab, const uint64_t* seg, const uint32_t* num_bits, const uint32_t* num_hashes,
                             uint8_t* blocks, uint64_t blocks_cap, uint64_t* block_off);
 
+/* ---- batched build from the tables' data blocks --------------------------- */
+/* A table written long ago keeps its keys in one place only: inside its data blocks, interleaved
+ * with the values,
+ *   [klen u16][vlen u16][key][value] ... [off u16 ...][n u16]
+ * (src/sstable/block/builder.rs:40-76; read back by Block::decode / key_at,
+ * src/sstable/block/reader.rs:18-44).  These entry points take such blocks as the key source and
+ * build ntab filters in one launch per geometry class, so that a filter the census finds saturated
+ * (lsmb_lset_census; src/sstable/builder.rs:51,74 sizes every one new(1000, 0.01), and
+ * src/compaction/scheduler.rs:147-160 writes a whole compaction into one), a bloom block that failed
+ * its CRC, a level rewritten with another false-positive rate or the inputs of a compaction read
+ * as whole files (scheduler.rs:91-103) are rebuilt without a host parse.  The caller uploads the
+ * files' data regions as they stand and names the blocks: block b is bytes[blk_off[b] ..
+ * blk_off[b] + blk_len[b]) (the index entries' offset and size, src/sstable/footer.rs:20-27), at
+ * any byte alignment; table t is the blocks [bseg[t], bseg[t+1]), bseg non-decreasing with
+ * bseg[ntab] <= nblk.  Blocks outside every table are ignored.
+ *
+ * A block is well-formed when len >= 2, with n = the u16 at len - 2: 2 + 2n <= len, and with
+ * data_end = len - 2 - 2n, for every i < n, off = the u16 at data_end + 2i, klen = the u16 at off,
+ * vlen = the u16 at off + 2: off + 4 <= data_end and off + 4 + klen + vlen <= data_end.  Nothing
+ * else is asked: offsets need not ascend, entries may overlap, empty keys and the keys of empty
+ * values (tombstones: builder.rs:93 adds the key first) count, a key present twice sets its bits
+ * twice, and a single-entry block may exceed 65 535 bytes (block/builder.rs:45).  No byte outside a
+ * block is read, whatever its bytes are.  A malformed block is not an error of the device call: its
+ * table's words are unspecified (only that table's slot is written, every other table is exact),
+ * and the block is reported as LSMB_SST_BAD_BLOCK.
+ *
+ * Output: the packed layout of lsmb_build_batch_dev, so lsmb_lset_add_batch_dev takes it as it is. */
+#define LSMB_SST_BAD_BLOCK 0xFFFFFFFFu
+
+/* Work items the plan gives a table of `blocks` data blocks holding `bytes` bytes in a filter of
+ * num_bits (src/sstable/block/builder.rs:40-76 blocks): >= 1, non-decreasing in bytes, at most one
+ * per block.  For tests and tools, like lsmb_build_batch_parts, and under the same switches plus
+ * two of its own, read at every call (tools/mb_build_batch_sst.py): LSMB_SST_WAVE_BYTES and
+ * LSMB_SST_GROUP_BYTES, the block bytes one item of each class walks (default 256 KiB and 1 MiB).
+ * The filter bits never depend on them. */
+int lsmb_build_batch_sst_parts(uint64_t blocks, uint64_t bytes, uint32_t num_bits);
+
+/* Device bytes (nbytes of them), host blk_off[nblk], blk_len[nblk], bseg[ntab + 1], num_bits[ntab],
+ * num_hashes[ntab]; d_words: device, 16-byte aligned, words_cap u64 words; d_blk_entries: device
+ * uint32_t[nblk] or NULL: entry b = block b's entry count, or LSMB_SST_BAD_BLOCK, for every block
+ * of a table (one plain store by the wave that owns the block; unclaimed blocks' entries are left
+ * as they were).  src/sstable/builder.rs:93 for every key of src/sstable/block/builder.rs:40-76's
+ * blocks.  Asynchronous on `stream`, no host synchronisation inside; the work list and the blocks'
+ * descriptors are staged as lsmb_build_batch_dev stages its own.  LSMB_EINVAL, nothing written:
+ * NULL ctx, bseg, num_bits, num_hashes or d_words; NULL blk_off or blk_len with nblk > 0; NULL
+ * d_bytes with a non-empty claimed block; bseg descending or bseg[ntab] > nblk; a claimed block
+ * with blk_off + blk_len > nbytes (checked here, so the device never sees a block that leaves the
+ * buffer); words_cap < word_off[ntab]; d_words not 16-byte aligned; num_bits == 0 with num_hashes
+ * > 0; a table above lsmb_build_batch_max_bits() (lsmb_last_error() names the table).  ntab == 0:
+ * LSMB_OK, nothing written. */
+int lsmb_build_batch_sst_dev(lsmb_ctx* ctx, const void* d_bytes, uint64_t nbytes, uint64_t nblk,
+                             const uint64_t* blk_off, const uint32_t* blk_len, uint64_t ntab, const uint64_t* bseg,
+                             const uint32_t* num_bits, const uint32_t* num_hashes, void* d_words, uint64_t words_cap,
+                             void* d_blk_entries, void* stream);
+
+/* Host bytes in, serialized bloom blocks out, synchronous: blooms[bloom_off[t] .. bloom_off[t+1]) =
+ * BloomFilter::serialize (src/sstable/builder.rs:177-182) of table t.  bloom_off[ntab + 1] is
+ * always filled when the other arguments pass; blooms == NULL or blooms_cap < bloom_off[ntab] is
+ * then LSMB_EINVAL, so a first call may ask for the size (as lsmb_build_batch_blocks).  entries
+ * (uint64_t[ntab], may be NULL): the sum of the table's block entry counts — what the meta block's
+ * entry_count (builder.rs:139-162) says of an intact table.  status (int32_t[ntab], may be NULL):
+ * LSMB_OK, or LSMB_ECORRUPT for a table with a malformed block; the return value is the first
+ * status that is not LSMB_OK, and lsmb_last_error() names that table and block.  The bloom bytes of
+ * a corrupt table are unspecified, every other table's are exact.  No host fallback: a NULL ctx is
+ * LSMB_EINVAL.  Other errors as lsmb_build_batch_sst_dev, with every output untouched. */
+int lsmb_build_batch_sst_blocks(lsmb_ctx* ctx, const uint8_t* bytes, uint64_t nbytes, uint64_t nblk,
+                                const uint64_t* blk_off, const uint32_t* blk_len, uint64_t ntab, const uint64_t* bseg,
+                                const uint32_t* num_bits, const uint32_t* num_hashes, uint8_t* blooms,
+                                uint64_t blooms_cap, uint64_t* bloom_off, uint64_t* entries, int32_t* status);
+
 /* CRC-32 of bloom blocks (optional checksum; the reference's
  * bloom block has none).  The same CRC as crc32fast::hash / zlib.crc32, which
  * the store already uses for WAL records and the manifest

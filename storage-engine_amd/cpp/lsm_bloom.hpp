@@ -126,6 +126,38 @@ class Context {
         return blocks;
     }
 
+    // The same filters straight from written tables' data blocks
+    // (lsmb_build_batch_sst_blocks; src/sstable/block/builder.rs:40-76's
+    // format, src/sstable/builder.rs:93 for every key in them): block b =
+    // bytes[blk_off[b] .. blk_off[b] + blk_len[b]), table t = the blocks
+    // [bseg[t], bseg[t+1]).  Returns each table's serialized bloom block;
+    // entries (optional) receives each table's entry count.  A table with a
+    // malformed block throws Corruption naming it.  Always on the GPU.
+    std::vector<std::vector<uint8_t>> build_batch_sst_blocks(const std::vector<uint8_t>& bytes,
+                                                             const std::vector<uint64_t>& blk_off,
+                                                             const std::vector<uint32_t>& blk_len,
+                                                             const std::vector<uint64_t>& bseg,
+                                                             const std::vector<uint32_t>& num_bits,
+                                                             const std::vector<uint32_t>& num_hashes,
+                                                             std::vector<uint64_t>* entries = nullptr) {
+        const size_t ntab = num_bits.size();
+        if (bseg.size() != ntab + 1 || num_hashes.size() != ntab || blk_off.size() != blk_len.size())
+            throw std::invalid_argument(
+                "build_batch_sst_blocks: bseg needs ntab + 1 entries, num_hashes ntab, blk_off and blk_len one per block");
+        std::vector<uint64_t> boff(ntab + 1, 0), ent(ntab, 0);
+        uint64_t total = 0;
+        for (uint32_t nb : num_bits) total += lsmb_serialized_size(nb);
+        std::vector<uint8_t> flat(total + 1);
+        const uint8_t none = 0;
+        check(lsmb_build_batch_sst_blocks(c_, bytes.empty() ? &none : bytes.data(), bytes.size(), blk_off.size(),
+                                          blk_off.data(), blk_len.data(), ntab, bseg.data(), num_bits.data(),
+                                          num_hashes.data(), flat.data(), total, boff.data(), ent.data(), nullptr));
+        if (entries) *entries = ent;
+        std::vector<std::vector<uint8_t>> blocks(ntab);
+        for (size_t t = 0; t < ntab; t++) blocks[t].assign(flat.begin() + boff[t], flat.begin() + boff[t + 1]);
+        return blocks;
+    }
+
    private:
     lsmb_ctx* c_ = nullptr;
 };

@@ -19,30 +19,11 @@
 // stores, so nothing is zeroed beforehand and no global atomic is used.  Only
 // the parts of a table split over several items OR their non-zero words in
 // with atomicOr, after k_bb_zero cleared just those slots.
-#include "build_batch_plan.hpp"
-#include "kernels.hpp"
+#include "build_batch_dev.hpp"
 #include "keysrc.hpp"
 
 namespace lsmb {
 namespace {
-
-static_assert(kBbMaxWords32 == kLdsFilterMaxWords32, "the batch accepts the LDS class");
-static_assert(kBbLdsBytes == kLdsBytes, "LDS per CU");
-static_assert(kBbMaxWords32 * 4 <= kBbLdsBytes, "a group item's image fits the LDS");
-static_assert((kBbWaveMaxBits / 32) * 4 * kBbWavesPerGroup <= kBbLdsBytes, "four wave regions fit the LDS");
-
-// Between an item's phases.  group: the workgroup's barrier.  wave: the 64
-// lanes run in lock step and the LDS serves one wave's operations in order,
-// so the compiler alone has to be kept from moving LDS accesses across.
-template <bool kGroup>
-__device__ __forceinline__ void bb_sync() {
-    if constexpr (kGroup) {
-        __syncthreads();
-    } else {
-        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-        __builtin_amdgcn_wave_barrier();
-    }
-}
 
 template <class Src, bool kGroup>
 __global__ __launch_bounds__(kGroup ? kBbGroupLanes : kBbWaveLanes * kBbWavesPerGroup) void k_build_batch(
@@ -54,11 +35,9 @@ __global__ __launch_bounds__(kGroup ? kBbGroupLanes : kBbWaveLanes * kBbWavesPer
     if (idx >= nitems) return;  // whole waves; the wave class meets no workgroup barrier
     const uint32_t lane = kGroup ? threadIdx.x : threadIdx.x % kBbWaveLanes;
     uint32_t* f = bb_lds + (kGroup ? 0u : wave * region32);  // region32 is a multiple of 4: 16-byte aligned
-    uint4* f4 = reinterpret_cast<uint4*>(f);
-    const BbItem it = items[idx];
-    const uint32_t nq = it.nw32 / 4;  // <= region32 / 4 (host: region32 = the launch's largest nw32)
+    const BbItem it = items[idx];  // nw32 <= region32 (host: region32 = the launch's largest nw32)
 
-    for (uint32_t q = lane; q < nq; q += L) f4[q] = make_uint4(0, 0, 0, 0);
+    bb_image_clear(f, it, lane, L);
     bb_sync<kGroup>();
 
     // the next key's load (its offsets, for var-len keys) is in flight while this one is hashed and walked
@@ -77,23 +56,7 @@ __global__ __launch_bounds__(kGroup ? kBbGroupLanes : kBbWaveLanes * kBbWavesPer
     }
     bb_sync<kGroup>();
 
-    uint32_t* dst = gw + 2 * it.dst;
-    if (it.parts == 1) {
-        uint4* dst4 = reinterpret_cast<uint4*>(dst);  // the buffer and every slot are 16-byte aligned
-        for (uint32_t q = lane; q < nq; q += L) dst4[q] = f4[q];
-    } else {
-        for (uint32_t w = lane; w < it.nw32; w += L) {
-            const uint32_t v = f[w];
-            if (v) atomicOr(dst + w, v);
-        }
-    }
-}
-
-// The slots of the multi-part tables (one item each), cleared before their parts OR in.
-__global__ __launch_bounds__(256) void k_bb_zero(const BbItem* __restrict__ items, uint32_t* __restrict__ gw) {
-    const BbItem it = items[blockIdx.x];
-    uint4* dst4 = reinterpret_cast<uint4*>(gw + 2 * it.dst);
-    for (uint32_t q = threadIdx.x; q < it.nw32 / 4; q += 256) dst4[q] = make_uint4(0, 0, 0, 0);
+    bb_image_out(f, it, gw, lane, L);
 }
 
 template <class Src>

@@ -88,17 +88,18 @@ struct BbPlan {
     uint32_t group_region32 = 0;     // the same for the group launch
 };
 
-// The work list of ntab tables, table t built from keys [seg[t], seg[t+1]) into
-// (num_bits[t], num_hashes[t]).  The arguments are the caller's to validate
-// (seg non-decreasing, num_bits <= kBbMaxBits, num_bits > 0 unless k == 0).
-inline BbPlan bb_plan(uint64_t ntab, const uint64_t* seg, const uint32_t* num_bits, const uint32_t* num_hashes,
-                      uint32_t wave_max_bits = kBbWaveMaxBits) {
+// The work list of ntab tables, table t built from the units [seg[t], seg[t+1])
+// of a run (keys here; data blocks in sst_blocks.hpp) into (num_bits[t],
+// num_hashes[t]), split into parts_of(t) >= 1 parts of equal unit counts.
+template <class PartsOf>
+inline BbPlan bb_plan_by(uint64_t ntab, const uint64_t* seg, const uint32_t* num_bits, const uint32_t* num_hashes,
+                         uint32_t wave_max_bits, PartsOf&& parts_of) {
     BbPlan pl;
     pl.word_off.resize(ntab + 1);
     bb_layout(ntab, num_bits, pl.word_off.data());
     for (uint64_t t = 0; t < ntab; t++) {
         const uint64_t keys = seg[t + 1] - seg[t];
-        const uint32_t parts = bb_parts(keys, num_bits[t], wave_max_bits);
+        const uint32_t parts = parts_of(t);
         const uint64_t per = keys / parts + (keys % parts != 0);
         const bool wave = bb_is_wave(num_bits[t], wave_max_bits);
         BbItem it;
@@ -118,6 +119,15 @@ inline BbPlan bb_plan(uint64_t ntab, const uint64_t* seg, const uint32_t* num_bi
         }
     }
     return pl;
+}
+
+// The work list of ntab tables, table t built from keys [seg[t], seg[t+1]) into
+// (num_bits[t], num_hashes[t]).  The arguments are the caller's to validate
+// (seg non-decreasing, num_bits <= kBbMaxBits, num_bits > 0 unless k == 0).
+inline BbPlan bb_plan(uint64_t ntab, const uint64_t* seg, const uint32_t* num_bits, const uint32_t* num_hashes,
+                      uint32_t wave_max_bits = kBbWaveMaxBits) {
+    return bb_plan_by(ntab, seg, num_bits, num_hashes, wave_max_bits,
+                      [&](uint64_t t) { return bb_parts(seg[t + 1] - seg[t], num_bits[t], wave_max_bits); });
 }
 
 // ---- the transform, serially ---------------------------------------------------

@@ -1,18 +1,19 @@
 // capi_build_batch.hip — the C ABI of the batched build (lsmb_build_batch_*,
 // include/lsmbloom.h).  Host-side plumbing only; the plan is in
-// build_batch_plan.hpp, the kernels in build_batch.hip.
+// build_batch_plan.hpp, the kernels in build_batch.hip; from data blocks
+// (lsmb_build_batch_sst_*), in sst_blocks.hpp and build_batch_sst.hip.
 #include <stdlib.h>
 #include <string.h>
 
 #include <algorithm>
 #include <string>
+#include <vector>
 
 #include "build_batch_plan.hpp"
 #include "ctx.hpp"
+#include "sst_blocks.hpp"
 
 using namespace lsmb;
-
-extern "C" {
 
 // ---------------------------------------------------------------- batched build
 // Many tables' filters from one key run (build_batch_plan.hpp, build_batch.hip):
@@ -62,11 +63,16 @@ int bb_check(uint64_t n, uint64_t ntab, const uint64_t* seg, const uint32_t* num
     return LSMB_OK;
 }
 
-// The plan's items through a staging slot to the device and the launches, all
-// on st; nothing is synchronised but the slot's own reuse (see lsmb_ctx).
-int bb_enqueue(lsmb_ctx* c, const KeyBatch& kb, const BbPlan& pl, uint64_t* d_words, hipStream_t st) {
+// The plan's items (and `tail`, further descriptors the launches read, behind
+// them) through a staging slot to the device and the launches, all on st;
+// nothing is synchronised but the slot's own reuse (see lsmb_ctx).
+// launch(d_items, d_tail, done) -> hipError_t enqueues the kernels.
+template <class Launch>
+int bb_enqueue_with(lsmb_ctx* c, const BbPlan& pl, const void* tail, size_t tail_bytes, hipStream_t st,
+                    const char* what, Launch&& launch) {
     const size_t nz = pl.zero.size(), nw = pl.wave.size(), ng = pl.group.size();
-    const size_t bytes = (nz + nw + ng) * sizeof(BbItem);
+    const size_t ibytes = (nz + nw + ng) * sizeof(BbItem);  // (items are 64 B: the tail stays aligned)
+    const size_t bytes = ibytes + tail_bytes;
     const int s = c->bb_slot;
     c->bb_slot ^= 1;
     if (!c->bb_done[s])
@@ -79,20 +85,114 @@ int bb_enqueue(lsmb_ctx* c, const KeyBatch& kb, const BbPlan& pl, uint64_t* d_wo
     if (nz) memcpy(h, pl.zero.data(), nz * sizeof(BbItem));
     if (nw) memcpy(h + nz, pl.wave.data(), nw * sizeof(BbItem));
     if (ng) memcpy(h + nz + nw, pl.group.data(), ng * sizeof(BbItem));
+    if (tail_bytes) memcpy(c->bb_pin[s] + ibytes, tail, tail_bytes);
     if (c->bb_stream[s] && c->bb_stream[s] != st) HIP_TRY(hipStreamWaitEvent(st, c->bb_done[s], 0));
     HIP_TRY(hipMemcpyAsync(c->bb_items[s].p, h, bytes, hipMemcpyHostToDevice, st));
-    const hipError_t e = launch_build_batch(kb, (const BbItem*)c->bb_items[s].p, (uint32_t)nz, (uint32_t)nw,
-                                            (uint32_t)ng, pl.wave_region32, pl.group_region32, bb_group_lanes(), d_words,
-                                            st, c->bb_done[s]);
+    const uint8_t* d = (const uint8_t*)c->bb_items[s].p;
+    const hipError_t e = launch((const BbItem*)d, d + ibytes, c->bb_done[s]);
     c->bb_stream[s] = st;
     if (e != hipSuccess) {
         (void)hipEventRecord(c->bb_done[s], st);  // (a failed launch may not have completed the event)
-        return hip_fail(e, "launch_build_batch");
+        return hip_fail(e, what);
     }
     return LSMB_OK;
 }
 
+int bb_enqueue(lsmb_ctx* c, const KeyBatch& kb, const BbPlan& pl, uint64_t* d_words, hipStream_t st) {
+    return bb_enqueue_with(c, pl, nullptr, 0, st, "launch_build_batch",
+                           [&](const BbItem* d_items, const uint8_t*, hipEvent_t done) {
+                               return launch_build_batch(kb, d_items, (uint32_t)pl.zero.size(), (uint32_t)pl.wave.size(),
+                                                         (uint32_t)pl.group.size(), pl.wave_region32, pl.group_region32,
+                                                         bb_group_lanes(), d_words, st, done);
+                           });
+}
+
+// ---- from data blocks (sst_blocks.hpp, build_batch_sst.hip) -----------------------
+// Measurement switches of tools/mb_build_batch_sst.py, read at every call: the
+// block bytes one item walks, per class (LSMB_SST_WAVE_BYTES, LSMB_SST_GROUP_BYTES),
+// beside the batched build's own.  The filter bits never depend on them.
+SstBounds bbs_bounds() {
+    SstBounds bd;
+    if (const char* s = getenv("LSMB_SST_WAVE_BYTES")) bd.wave_bytes = strtoull(s, nullptr, 10);
+    if (const char* s = getenv("LSMB_SST_GROUP_BYTES")) bd.group_bytes = strtoull(s, nullptr, 10);
+    bd.wave_max_bits = bb_wave_max_bits();
+    return bd;
+}
+
+// What lsmb_build_batch_sst_* check before anything is written or any of the
+// bytes is read; `bytes` is only compared with NULL.
+int bbs_check(const void* bytes, uint64_t nbytes, uint64_t nblk, const uint64_t* blk_off, const uint32_t* blk_len,
+              uint64_t ntab, const uint64_t* bseg, const uint32_t* num_bits, const uint32_t* num_hashes) {
+    if (!bseg || !num_bits || !num_hashes)
+        return fail(LSMB_EINVAL, "batched build from blocks: null bseg, num_bits or num_hashes");
+    if (nblk && (!blk_off || !blk_len)) return fail(LSMB_EINVAL, "batched build from blocks: null blk_off or blk_len");
+    if (ntab >= (1ull << 31)) return fail(LSMB_EINVAL, "batched build from blocks: more than 2^31-1 tables");
+    for (uint64_t t = 0; t < ntab; t++)
+        if (bseg[t + 1] < bseg[t])
+            return fail(LSMB_EINVAL, "batched build from blocks: bseg descends at table %llu", (unsigned long long)t);
+    if (bseg[ntab] > nblk)
+        return fail(LSMB_EINVAL, "batched build from blocks: bseg[ntab] = %llu is past the %llu blocks",
+                    (unsigned long long)bseg[ntab], (unsigned long long)nblk);
+    if (bseg[ntab] - bseg[0] >= (1ull << 31))
+        return fail(LSMB_EINVAL, "batched build from blocks: more than 2^31-1 blocks");
+    for (uint64_t t = 0; t < ntab; t++) {
+        if (check_filter(num_bits[t], num_hashes[t]) != LSMB_OK) {
+            const std::string msg = last_error();
+            return fail(LSMB_EINVAL, "batched build from blocks: table %llu: %s", (unsigned long long)t, msg.c_str());
+        }
+        if (num_bits[t] > kBbMaxBits)
+            return fail(LSMB_EINVAL,
+                        "batched build from blocks: table %llu has %u bits, above lsmb_build_batch_max_bits() = %u",
+                        (unsigned long long)t, num_bits[t], kBbMaxBits);
+        // the device never sees a block that leaves the buffer
+        for (uint64_t b = bseg[t]; b < bseg[t + 1]; b++) {
+            if (blk_off[b] > nbytes || blk_len[b] > nbytes - blk_off[b])
+                return fail(LSMB_EINVAL,
+                            "batched build from blocks: table %llu: block %llu (%llu + %u) leaves the %llu bytes",
+                            (unsigned long long)t, (unsigned long long)b, (unsigned long long)blk_off[b], blk_len[b],
+                            (unsigned long long)nbytes);
+            if (blk_len[b] && !bytes) return fail(LSMB_EINVAL, "batched build from blocks: null bytes");
+        }
+    }
+    return LSMB_OK;  // (a table has at most one part per block: fewer than 2^31 work items)
+}
+
+// The claimed blocks [bseg[0], bseg[ntab]) renumbered from 0: their descriptors
+// (offsets less `origin`) and the plan over them.
+struct BbsWork {
+    std::vector<SstBlk> blks;
+    BbPlan pl;
+};
+BbsWork bbs_work(const uint64_t* blk_off, const uint32_t* blk_len, uint64_t ntab, const uint64_t* bseg,
+                 const uint32_t* num_bits, const uint32_t* num_hashes, uint64_t origin) {
+    BbsWork w;
+    const uint64_t b0 = bseg[0], nb = bseg[ntab] - b0;
+    w.blks.resize(nb);
+    for (uint64_t b = 0; b < nb; b++) w.blks[b] = SstBlk{blk_off[b0 + b] - origin, blk_len[b0 + b], 0};
+    std::vector<uint64_t> seg(ntab + 1);
+    for (uint64_t t = 0; t <= ntab; t++) seg[t] = bseg[t] - b0;
+    w.pl = sst_plan(nb ? blk_len + b0 : nullptr, ntab, seg.data(), num_bits, num_hashes, bbs_bounds());
+    return w;
+}
+
+// d_blk_entries: of the claimed blocks, renumbered like the descriptors.
+int bbs_enqueue(lsmb_ctx* c, const uint8_t* d_bytes, const BbsWork& w, uint64_t* d_words, uint32_t* d_blk_entries,
+                hipStream_t st) {
+    const BbPlan& pl = w.pl;
+    return bb_enqueue_with(c, pl, w.blks.data(), w.blks.size() * sizeof(SstBlk), st, "launch_build_batch_sst",
+                           [&](const BbItem* d_items, const uint8_t* d_tail, hipEvent_t done) {
+                               return launch_build_batch_sst(
+                                   d_bytes, (const SstBlk*)d_tail, d_items, (uint32_t)pl.zero.size(),
+                                   (uint32_t)pl.wave.size(), (uint32_t)pl.group.size(), pl.wave_region32,
+                                   pl.group_region32, bb_group_lanes(), d_words, d_blk_entries, st, done);
+                           });
+}
+
+static_assert(LSMB_SST_BAD_BLOCK == kSstBadBlock, "the header's value is the kernels'");
+
 }  // namespace
+
+extern "C" {
 
 uint32_t lsmb_build_batch_max_bits(void) { return kBbMaxBits; }
 
@@ -161,6 +261,92 @@ int lsmb_build_batch_blocks(lsmb_ctx* c, const uint8_t* data, const uint64_t* of
         if (nw) memcpy(b + 12, c->bb_host + pl.word_off[t] * 8, nw * 8);
     }
     return LSMB_OK;
+}
+
+// ---------------------------------------------------------------- from data blocks
+int lsmb_build_batch_sst_parts(uint64_t blocks, uint64_t bytes, uint32_t num_bits) {
+    return (int)sst_parts(blocks, bytes, num_bits, bbs_bounds());
+}
+
+int lsmb_build_batch_sst_dev(lsmb_ctx* c, const void* d_bytes, uint64_t nbytes, uint64_t nblk, const uint64_t* blk_off,
+                             const uint32_t* blk_len, uint64_t ntab, const uint64_t* bseg, const uint32_t* num_bits,
+                             const uint32_t* num_hashes, void* d_words, uint64_t words_cap, void* d_blk_entries,
+                             void* stream) {
+    if (!c) return fail(LSMB_EINVAL, "null ctx");
+    if (ntab == 0) return LSMB_OK;
+    if (int rc = bbs_check(d_bytes, nbytes, nblk, blk_off, blk_len, ntab, bseg, num_bits, num_hashes)) return rc;
+    if (!d_words) return fail(LSMB_EINVAL, "batched build from blocks: null d_words");
+    if (reinterpret_cast<uintptr_t>(d_words) & 15)
+        return fail(LSMB_EINVAL, "batched build from blocks: d_words is not 16-byte aligned");
+    const BbsWork w = bbs_work(blk_off, blk_len, ntab, bseg, num_bits, num_hashes, 0);
+    if (words_cap < w.pl.word_off[ntab])
+        return fail(LSMB_EINVAL, "batched build from blocks: words_cap %llu < the layout's %llu words",
+                    (unsigned long long)words_cap, (unsigned long long)w.pl.word_off[ntab]);
+    DevGuard g(c->dev);
+    uint32_t* ent = d_blk_entries ? (uint32_t*)d_blk_entries + bseg[0] : nullptr;
+    return bbs_enqueue(c, (const uint8_t*)d_bytes, w, (uint64_t*)d_words, ent, pick_stream(c, stream));
+}
+
+int lsmb_build_batch_sst_blocks(lsmb_ctx* c, const uint8_t* bytes, uint64_t nbytes, uint64_t nblk,
+                                const uint64_t* blk_off, const uint32_t* blk_len, uint64_t ntab, const uint64_t* bseg,
+                                const uint32_t* num_bits, const uint32_t* num_hashes, uint8_t* blooms,
+                                uint64_t blooms_cap, uint64_t* bloom_off, uint64_t* entries, int32_t* status) {
+    if (!c) return fail(LSMB_EINVAL, "null ctx: the batched build runs on the GPU whatever the block count");
+    if (!bloom_off) return fail(LSMB_EINVAL, "batched build from blocks: null bloom_off");
+    if (ntab == 0) {
+        bloom_off[0] = 0;
+        return LSMB_OK;
+    }
+    if (int rc = bbs_check(bytes, nbytes, nblk, blk_off, blk_len, ntab, bseg, num_bits, num_hashes)) return rc;
+    bloom_off[0] = 0;
+    for (uint64_t t = 0; t < ntab; t++) bloom_off[t + 1] = bloom_off[t] + 12 + 8 * nwords64(num_bits[t]);
+    if (!blooms || blooms_cap < bloom_off[ntab])
+        return fail(LSMB_EINVAL, "batched build from blocks: blooms buffer %llu B < the %llu B of the batch's blocks",
+                    (unsigned long long)(blooms ? blooms_cap : 0), (unsigned long long)bloom_off[ntab]);
+    DevGuard g(c->dev);
+    // the bytes the claimed blocks span cross once, the blocks renumbered and rebased onto them
+    const uint64_t b0 = bseg[0], nb = bseg[ntab] - b0;
+    uint64_t lo = nbytes, hi = 0;
+    for (uint64_t b = b0; b < b0 + nb; b++)
+        if (blk_len[b]) {
+            lo = std::min(lo, blk_off[b]);
+            hi = std::max(hi, blk_off[b] + blk_len[b]);
+        }
+    if (hi < lo) lo = hi = 0;
+    const BbsWork w = bbs_work(blk_off, blk_len, ntab, bseg, num_bits, num_hashes, lo);
+    const uint64_t wbytes = w.pl.word_off[ntab] * 8, obytes = wbytes + nb * 4;  // the words, then the blocks' counts
+    HIP_TRY(c->keys.ensure(hi - lo + 16));
+    if (hi > lo) HIP_TRY(hipMemcpyAsync(c->keys.p, bytes + lo, hi - lo, hipMemcpyHostToDevice, c->st));
+    HIP_TRY(c->bb_words.ensure(obytes));
+    if (int rc = pinned_ensure(c->pinned_retired, &c->bb_host, &c->bb_host_cap, obytes, "batched build")) return rc;
+    if (int rc = bbs_enqueue(c, (const uint8_t*)c->keys.p, w, (uint64_t*)c->bb_words.p,
+                             (uint32_t*)((uint8_t*)c->bb_words.p + wbytes), c->st))
+        return rc;
+    HIP_TRY(hipMemcpyAsync(c->bb_host, c->bb_words.p, obytes, hipMemcpyDeviceToHost, c->st));
+    HIP_TRY(hipStreamSynchronize(c->st));
+    const uint32_t* got = (const uint32_t*)(c->bb_host + wbytes);
+    int first = LSMB_OK;
+    for (uint64_t t = 0; t < ntab; t++) {
+        uint8_t* out = blooms + bloom_off[t];
+        write_header(out, num_bits[t], num_hashes[t]);
+        const uint64_t nw = nwords64(num_bits[t]);
+        if (nw) memcpy(out + 12, c->bb_host + w.pl.word_off[t] * 8, nw * 8);
+        uint64_t sum = 0;
+        int st_t = LSMB_OK;
+        for (uint64_t b = bseg[t]; b < bseg[t + 1]; b++) {
+            if (got[b - b0] != LSMB_SST_BAD_BLOCK) {
+                sum += got[b - b0];
+                continue;
+            }
+            if (st_t == LSMB_OK && first == LSMB_OK)
+                first = fail(LSMB_ECORRUPT, "batched build from blocks: table %llu: block %llu is malformed",
+                             (unsigned long long)t, (unsigned long long)b);
+            st_t = LSMB_ECORRUPT;
+        }
+        if (entries) entries[t] = sum;
+        if (status) status[t] = st_t;
+    }
+    return first;
 }
 
 }  // extern "C"

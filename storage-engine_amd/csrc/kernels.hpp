@@ -158,6 +158,18 @@ hipError_t launch_build_batch(const KeyBatch& kb, const BbItem* d_items, uint32_
                               uint32_t ngroup, uint32_t wave_region32, uint32_t group_region32, uint32_t group_lanes,
                               uint64_t* d_words, hipStream_t st, hipEvent_t done = nullptr);
 
+// The batched build over data blocks (build_batch_sst.hip; block format, plan
+// and descriptors in sst_blocks.hpp): the same item list, an item's key_lo /
+// key_hi naming the blocks [block_lo, block_hi) of d_blks, every one of them
+// inside d_bytes (the caller has checked).  Writes the slots the items name inside d_words and, when
+// d_blk_entries is non-null, d_blk_entries[b] = block b's entry count or
+// LSMB_SST_BAD_BLOCK for every block of an item; nothing else.
+struct SstBlk;
+hipError_t launch_build_batch_sst(const uint8_t* d_bytes, const SstBlk* d_blks, const BbItem* d_items,
+                                  uint32_t nzero, uint32_t nwave, uint32_t ngroup, uint32_t wave_region32,
+                                  uint32_t group_region32, uint32_t group_lanes, uint64_t* d_words,
+                                  uint32_t* d_blk_entries, hipStream_t st, hipEvent_t done = nullptr);
+
 // out[i] bit s = (lo_s <= key i <= hi_s) && may_contain(filter s, key i), for
 // the nfilt (<= 64) descriptors at d_filters (device memory).  One class
 // holding every descriptor takes the bit-sliced kernel with a compile-time

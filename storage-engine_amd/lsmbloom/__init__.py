@@ -32,6 +32,7 @@ LSMB_ECORRUPT = -4
 LSMB_ENOMEM = -5
 LSMB_LSET_MAX_LEVELS = 8
 LSMB_LSET_NONE = 0xFFFFFFFF  # LevelSet.probe: no table of this row
+LSMB_SST_BAD_BLOCK = 0xFFFFFFFF  # build_batch_sst_dev: a malformed data block's blk_entries
 LSMB_LSET_REPACK_ALL = 1000001  # LevelSet.derive(repack="all"): every surviving table moves
 LSMB_LSET_ROW_L0 = 0x80000000  # `row` of any LevelSet add: the table goes to the set's L0 part
 LSMB_LSET_L0_MAX = 64
@@ -166,6 +167,12 @@ SIGNATURES = {
                                             u32p, vp, ctypes.c_uint64, vp]),
     "lsmb_build_batch_blocks": (ctypes.c_int, [vp, u8p, u64p, ctypes.c_uint32, ctypes.c_uint64, ctypes.c_uint64, u64p,
                                                u32p, u32p, u8p, ctypes.c_uint64, u64p]),
+    "lsmb_build_batch_sst_parts": (ctypes.c_int, [ctypes.c_uint64, ctypes.c_uint64, ctypes.c_uint32]),
+    "lsmb_build_batch_sst_dev": (ctypes.c_int, [vp, vp, ctypes.c_uint64, ctypes.c_uint64, u64p, u32p, ctypes.c_uint64,
+                                                u64p, u32p, u32p, vp, ctypes.c_uint64, vp, vp]),
+    "lsmb_build_batch_sst_blocks": (ctypes.c_int, [vp, u8p, ctypes.c_uint64, ctypes.c_uint64, u64p, u32p,
+                                                   ctypes.c_uint64, u64p, u32p, u32p, u8p, ctypes.c_uint64, u64p, u64p,
+                                                   ctypes.POINTER(ctypes.c_int32)]),
     "lsmb_multi_open": (ctypes.c_int, [ctypes.POINTER(vp), ctypes.POINTER(ctypes.c_int), ctypes.c_int]),
     "lsmb_multi_close": (None, [vp]),
     "lsmb_multi_size": (ctypes.c_int, [vp]),
@@ -520,6 +527,70 @@ class Context:
                                              _p(nb, u32p) if ntab else None, _p(kk, u32p) if ntab else None,
                                              _p(blocks, u8p), blocks.size, _p(boff, u64p)))
         return blocks[:int(boff[ntab])], boff
+
+    # The same filters straight from the tables' data blocks (src/sstable/block/builder.rs:40-76):
+    # block b = bytes[blk_off[b] .. blk_off[b] + blk_len[b]), table t = blocks [bseg[t], bseg[t+1]).
+    @staticmethod
+    def _sst_args(who, blk_off, blk_len, bseg, num_bits, num_hashes):
+        bo = np.ascontiguousarray(blk_off, dtype=np.uint64)
+        bl = np.ascontiguousarray(blk_len, dtype=np.uint32)
+        bseg = np.ascontiguousarray(bseg, dtype=np.uint64)
+        nb = np.ascontiguousarray(num_bits, dtype=np.uint32)
+        kk = np.ascontiguousarray(num_hashes, dtype=np.uint32)
+        if bo.size != bl.size:
+            raise ValueError("%s: blk_off and blk_len differ in length" % who)
+        if bseg.size != nb.size + 1 or kk.size != nb.size:
+            raise ValueError("%s: bseg needs ntab + 1 entries, num_hashes ntab" % who)
+        return bo, bl, bseg, nb, kk
+
+    def build_batch_sst_dev(self, bytes, blk_off, blk_len, bseg, num_bits, num_hashes, words, blk_entries=None,
+                            stream=None):
+        """lsmb_build_batch_sst_dev: bytes a uint8 device tensor holding the
+        blocks; blk_off, blk_len (nblk), bseg (ntab + 1), num_bits and
+        num_hashes (ntab) host sequences; words as build_batch_dev's;
+        blk_entries an int32 device tensor of nblk entries or None (entry b =
+        block b's entry count, LSMB_SST_BAD_BLOCK for a malformed block).
+        Asynchronous on stream.  Returns the layout (word_off, uint64)."""
+        bo, bl, bseg, nb, kk = self._sst_args("build_batch_sst_dev", blk_off, blk_len, bseg, num_bits, num_hashes)
+        if blk_entries is not None and blk_entries.numel() * blk_entries.element_size() < 4 * bo.size:
+            raise ValueError("build_batch_sst_dev: blk_entries needs one uint32 per block")
+        ntab, nblk = nb.size, bo.size
+        _check(lib().lsmb_build_batch_sst_dev(
+            self.h, vp(bytes.data_ptr()) if bytes is not None else None,
+            bytes.numel() * bytes.element_size() if bytes is not None else 0, nblk, _p(bo, u64p) if nblk else None,
+            _p(bl, u32p) if nblk else None, ntab, _p(bseg, u64p), _p(nb, u32p) if ntab else None,
+            _p(kk, u32p) if ntab else None, vp(words.data_ptr()), words.numel() * words.element_size() // 8,
+            vp(blk_entries.data_ptr()) if blk_entries is not None else None, self._stream(stream)))
+        return build_batch_layout(nb)
+
+    def build_batch_sst_blocks(self, bytes, blk_off, blk_len, bseg, num_bits, num_hashes):
+        """lsmb_build_batch_sst_blocks: host bytes holding the data blocks ->
+        (blooms, bloom_off, entries, status): the tables' serialized bloom
+        blocks back to back (uint8), their ntab + 1 offsets (uint64), each
+        table's entry count (uint64) and LSMB_OK or LSMB_ECORRUPT per table
+        (int32).  A malformed block is not raised: it is its table's status
+        (that table's bloom bytes are unspecified, every other table's exact),
+        and lsmb_last_error() names the first such table and block.  Runs on
+        the GPU whatever the block count."""
+        bo, bl, bseg, nb, kk = self._sst_args("build_batch_sst_blocks", blk_off, blk_len, bseg, num_bits, num_hashes)
+        data = np.ascontiguousarray(np.frombuffer(bytes, dtype=np.uint8) if not isinstance(bytes, np.ndarray) else bytes,
+                                    dtype=np.uint8).reshape(-1)
+        nbytes = data.size
+        if nbytes == 0:
+            data = np.zeros(1, np.uint8)
+        ntab, nblk = nb.size, bo.size
+        boff = np.zeros(ntab + 1, dtype=np.uint64)
+        blooms = np.empty(max(sum(serialized_size(int(b)) for b in nb), 1), dtype=np.uint8)
+        entries = np.zeros(ntab, dtype=np.uint64)
+        status = np.zeros(ntab, dtype=np.int32)
+        rc = lib().lsmb_build_batch_sst_blocks(
+            self.h, _p(data, u8p), nbytes, nblk, _p(bo, u64p) if nblk else None, _p(bl, u32p) if nblk else None, ntab,
+            _p(bseg, u64p), _p(nb, u32p) if ntab else None, _p(kk, u32p) if ntab else None, _p(blooms, u8p), blooms.size,
+            _p(boff, u64p), _p(entries, u64p) if ntab else None,
+            _p(status, ctypes.POINTER(ctypes.c_int32)) if ntab else None)
+        if rc != LSMB_ECORRUPT:
+            _check(rc)
+        return blooms[:int(boff[ntab])], boff, entries, status
 
     def probe_dev(self, filters, data, n, out, offsets=None, key_len=0, stream=None):
         """filters: [(words tensor on device, num_bits, k)]."""
@@ -1246,6 +1317,11 @@ def build_batch_layout(num_bits):
 def build_batch_parts(keys, num_bits):
     """Work items a batched build gives one table of this shape (lsmb_build_batch_parts)."""
     return int(lib().lsmb_build_batch_parts(int(keys), int(num_bits)))
+
+
+def build_batch_sst_parts(blocks, nbytes, num_bits):
+    """Work items a batched build from data blocks gives one table of this shape (lsmb_build_batch_sst_parts)."""
+    return int(lib().lsmb_build_batch_sst_parts(int(blocks), int(nbytes), int(num_bits)))
 
 
 def crc32(data, crc=0):

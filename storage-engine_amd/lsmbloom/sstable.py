@@ -14,8 +14,15 @@ and copies it straight into HBM) together with the table's [min_key, max_key]
 from the meta block, so DB::get's per-table checks (reader.rs:192-199) run as
 one batched GPU probe.
 
-Data blocks and the index entries' content are the SST builder's business and
-out of scope: callers pass the data-block end offset and the encoded index.
+Writing data blocks and the index stays the SST builder's business: on the write
+side callers pass the data-block end offset and the encoded index.  Reading them
+back is not: a table written long ago keeps its keys only inside its data
+blocks, so `read_blocks` follows the index (parse_index_block, footer.rs:46-70,
+reader.rs:70-76) to the data region and `rebuild_filters` builds right-sized
+filters for many such files straight from those bytes in one GPU call
+(lsmb_build_batch_sst_blocks) — what a saturated filter found by
+LevelSet.census, or a bloom block that failed its CRC, needs.  The blocks are
+parsed on the device; rewriting the file itself is not done here.
 """
 import io
 import os
@@ -90,6 +97,27 @@ def encode_index_entry(last_key, offset, size):
     """IndexEntry::encode (footer.rs:20-27): [key_len u16][last_key][offset u64][size u64]."""
     last_key = bytes(last_key)
     return struct.pack("<H", len(last_key)) + last_key + struct.pack("<QQ", offset, size)
+
+
+def parse_index_block(buf):
+    """The index block as SSTable::open reads it (reader.rs:70-76, a loop of
+    IndexEntry::decode, footer.rs:46-70) -> [(last_key, offset, size)].
+    Corruption on the reference's conditions: fewer than 2 bytes left for a
+    key length, or an entry running past the block."""
+    buf = bytes(buf)
+    out = []
+    at = 0
+    while at < len(buf):
+        if len(buf) - at < 2:
+            raise Corruption(-4, "index entry too short")
+        (klen,) = struct.unpack_from("<H", buf, at)
+        total = 2 + klen + 16
+        if len(buf) - at < total:
+            raise Corruption(-4, "index entry truncated")
+        offset, size = struct.unpack_from("<QQ", buf, at + 2 + klen)
+        out.append((buf[at + 2:at + 2 + klen], offset, size))
+        at += total
+    return out
 
 
 class KeyArena:
@@ -186,3 +214,59 @@ def load_filter(fset, path):
     FilterSet with the table's key range; returns the slot."""
     _, bloom, meta = read_tail(path)
     return fset.add(bloom, meta["min_key"], meta["max_key"])
+
+
+def read_blocks(path):
+    """A written table's data blocks as the batched build takes them ->
+    (data-region bytes uint8, blk_off uint64, blk_len uint32, meta dict): the
+    file's bytes before the meta block as they stand, and each index entry's
+    (offset, size) (footer.rs:20-27).  Corruption for an index that does not
+    parse, a block size past 32 bits or a block outside the data region."""
+    ft, _, meta = read_tail(path)
+    with open(path, "rb") as f:
+        region = f.read(ft.meta_block_offset)
+        f.seek(ft.index_block_offset)
+        index = f.read(ft.index_block_size)
+    if len(region) != ft.meta_block_offset or len(index) != ft.index_block_size:
+        raise Corruption(-4, "data region or index block truncated")
+    entries = parse_index_block(index)
+    for _, off, size in entries:
+        if size >= 1 << 32 or off + size > len(region):
+            raise Corruption(-4, "index entry names a block outside the data region")
+    return (np.frombuffer(region, dtype=np.uint8), np.array([e[1] for e in entries], dtype=np.uint64),
+            np.array([e[2] for e in entries], dtype=np.uint32), meta)
+
+
+def rebuild_filters(paths, fpr=0.01, ctx=None):
+    """Right-sized bloom blocks for written tables, from their data blocks: each
+    table's filter is BloomFilter::new(max(meta.entry_count, 1), fpr) over
+    every key of its blocks, all files in one lsmb_build_batch_sst_blocks call.
+    -> per path (bloom block bytes, num_bits, k, entries).  Corruption when a
+    table has a malformed block or its blocks hold another number of entries
+    than its meta block says."""
+    ctx = ctx or default_context()
+    regions, offs, lens, bseg, shapes, metas = [], [], [], [0], [], []
+    base = 0
+    for path in paths:
+        region, bo, bl, meta = read_blocks(path)
+        regions.append(region)
+        offs.append(bo + np.uint64(base))
+        lens.append(bl)
+        bseg.append(bseg[-1] + bo.size)
+        shapes.append(params(max(meta["entry_count"], 1), fpr))
+        metas.append(meta)
+        base += region.size
+    if not regions:
+        return []
+    blooms, boff, entries, status = ctx.build_batch_sst_blocks(
+        np.concatenate(regions), np.concatenate(offs), np.concatenate(lens), bseg, [s[0] for s in shapes],
+        [s[1] for s in shapes])
+    out = []
+    for t, path in enumerate(paths):
+        if status[t] != 0:
+            raise Corruption(int(status[t]), "%s: a data block is malformed" % path)
+        if int(entries[t]) != metas[t]["entry_count"]:
+            raise Corruption(-4, "%s: the data blocks hold %d entries, the meta block says %d"
+                             % (path, int(entries[t]), metas[t]["entry_count"]))
+        out.append((blooms[int(boff[t]):int(boff[t + 1])].tobytes(), shapes[t][0], shapes[t][1], int(entries[t])))
+    return out
