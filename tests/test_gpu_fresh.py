@@ -89,7 +89,11 @@ def test_fresh_overflow_side_buffer(ctx, oracle, filter_keys):
     not read) and pass B folds them in.  2^20-bit bins (one sweep) and the
     2^21-bit bins of C5's 2-sweep filter.  The overflow words must be all-zero
     again afterwards: an accumulate build with overflow and a clean fresh
-    build follow on the same context."""
+    build follow on the same context.
+
+    That rings, regions, lists and the side buffer are all reached is checked
+    in tests/test_partition_stage.py::test_pass_a_overflow_tiers (derived from
+    the plan, then counted per tier after pass A), not here."""
     import torch
     n = 10_000_000
     keys_h = keygen.key16(0xD00D, 0, n)

@@ -321,7 +321,12 @@ def test_overflow_levels(ctx, oracle, nb):
     16 384, so ring, region, overflow list and the ovf / dirty side buffer all
     engage, with 2^20-bit overflow units up to index 4095.  A fresh build on
     garbage, an accumulate build onto a preset (= ref | preset), then a clean
-    fresh build on the same context: no stale overflow bits remain."""
+    fresh build on the same context: no stale overflow bits remain.
+
+    That the tiers engage is argued here from kOvfListCap and the plans, not
+    checked: tests/test_partition_stage.py::test_pass_a_overflow_tiers derives
+    the claim from the plan, fails if it no longer holds, and counts the
+    entries of every tier after pass A."""
     n, k = 4_000_000, 7
     _plan(nb, n, k, "partition", 2)
     keys_h = _keys("K8")[:n].copy()
