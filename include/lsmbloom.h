@@ -382,6 +382,102 @@ int lsmb_build_batch_sst_blocks(lsmb_ctx* ctx, const uint8_t* bytes, uint64_t nb
                                 const uint32_t* num_bits, const uint32_t* num_hashes, uint8_t* blooms,
                                 uint64_t blooms_cap, uint64_t* bloom_off, uint64_t* entries, int32_t* status);
 
+/* ---- compaction: the surviving keys of merged data blocks -------------------- */
+/* A compaction's output table is not the union of its inputs.  MergeIterator keeps the newest version
+ * of each key, the lowest source index (src/iterator/merge.rs:15,55-56,98-121), and a bottommost
+ * compaction drops every key whose newest version is a tombstone (src/compaction/scheduler.rs:
+ * 147-158).  These entry points resolve that on the device from the data blocks the compaction has
+ * already read, and give what the rest of the engine needs of the merge: the survivor count (the
+ * output table's entry_count, and the n of BloomFilter::new(n, fpr)), the survivors' keys as a device
+ * key run (what lsmb_build_var_dev_new and lsmb_build_batch_dev take), and in one call the output
+ * table's bloom block.
+ *
+ * Input: the bytes and blocks of lsmb_build_batch_sst_dev (format and well-formed rule above,
+ * unchanged), cut into sources instead of tables: host sseg[nsrc + 1], non-decreasing, sseg[nsrc] <=
+ * nblk; source s is the blocks [sseg[s], sseg[s+1]); source 0 is the NEWEST (the order in which
+ * scheduler.rs:92-103 pushes task.inputs; merge.rs:15 "lower index = newer source").  Blocks outside
+ * every source are ignored.  A source is meant to be one SSTable: keys strictly ascending in unsigned
+ * byte-lexicographic order (Vec<u8>'s cmp, a proper prefix is smaller) across its entries and blocks.
+ *
+ * An entry e of source s SURVIVES when (1) no source s' < s holds an entry with a byte-equal key, and
+ * (2) drop_tombstones == 0, or e's vlen > 0.  For ascending sources this is exactly the set
+ * run_compaction hands to builder.add (scheduler.rs:152-158); drop_tombstones is its is_bottommost,
+ * which the caller decides (scheduler.rs:127-145).  Survivors are reported in (block index, entry
+ * index) order: the output is deterministic, no atomic decides a layout.
+ *
+ * The lookup in a newer source is the store's own (SSTable::get): a binary search of the source's
+ * blocks by each block's last key, then a binary search inside that block through its offset array.
+ * Every "shadowed" verdict rests on a byte-equal key actually found.  For sources that are not
+ * ascending a search may miss but can never hit falsely: the survivor set is then a SUPERSET of the
+ * right one, never a subset — extra filter bits, no false negative — and the call is still LSMB_OK.
+ *
+ * A claimed block that is malformed, or that holds no entries (the store never writes one,
+ * src/sstable/builder.rs:112-115, and the search needs a last key), is BAD: it is reported as
+ * LSMB_SST_BAD_BLOCK in d_blk_entries and counted in totals[3], holds no keys for any search (the
+ * other blocks' verdicts are as if it were absent) and contributes no survivors.  No byte outside a
+ * claimed block is read, whatever the bytes are, and every search terminates on any input. */
+
+/* The bytes of device work buffer a mark and gather over any sources cut from these nblk blocks need
+ * (src/compaction/scheduler.rs:91-103's inputs): per block a 24-byte descriptor, four u64 counters and
+ * one flag bit per entry the block could hold (entries may overlap, so blk_len / 2 of them: about
+ * blk_len / 16 bytes).  0 for NULL blk_len with nblk > 0. */
+uint64_t lsmb_compact_sst_work_bytes(uint64_t nblk, const uint32_t* blk_len);
+
+/* The mark (the merge of src/iterator/merge.rs:98-121 and the tombstone drop of src/compaction/
+ * scheduler.rs:152-158, as verdicts): device bytes, host blk_off[nblk], blk_len[nblk], sseg[nsrc + 1];
+ * d_work: device, 16-byte aligned, work_bytes >= lsmb_compact_sst_work_bytes of the claimed blocks;
+ * d_blk_entries: device uint32_t[nblk] or NULL: entry b = block b's entry count, or
+ * LSMB_SST_BAD_BLOCK, for every claimed block (unclaimed blocks' entries are left as they were);
+ * d_totals: device uint64_t[4], all four written in full: {survivors, the survivors' key bytes, the
+ * entries of the good claimed blocks, bad blocks}.  Asynchronous on `stream`, no host synchronisation
+ * inside; the blocks' descriptors are staged as lsmb_build_batch_sst_dev stages its own.
+ * LSMB_EINVAL, nothing written: NULL ctx, sseg, d_work or d_totals; NULL blk_off or blk_len with nblk
+ * > 0; NULL d_bytes with a non-empty claimed block; sseg descending or sseg[nsrc] > nblk; a claimed
+ * block with blk_off + blk_len > nbytes (checked here, so the device never sees a block that leaves
+ * the buffer); work_bytes too small; d_work not 16-byte aligned.  nsrc == 0: LSMB_OK, totals all
+ * zero. */
+int lsmb_compact_sst_mark_dev(lsmb_ctx* ctx, const void* d_bytes, uint64_t nbytes, uint64_t nblk,
+                              const uint64_t* blk_off, const uint32_t* blk_len, uint64_t nsrc, const uint64_t* sseg,
+                              int drop_tombstones, void* d_work, uint64_t work_bytes, void* d_blk_entries,
+                              void* d_totals, void* stream);
+
+/* The gather (the keys src/compaction/scheduler.rs:152-158 hands to builder.add, src/sstable/
+ * builder.rs:93, as a key run): after a mark of the same block and source arguments and the same
+ * d_work on the same stream, the survivors' keys back to back into d_key_data and survivors + 1
+ * uint64_t offsets into d_key_offsets (8-byte aligned), offsets[0] = 0, key i =
+ * d_key_data[offsets[i] .. offsets[i+1]).  The caller sizes both from the totals it read back:
+ * data_cap >= totals[1] bytes, offs_cap >= totals[0] + 1 offsets.  The mark's totals are the
+ * authority: with a capacity below them nothing is written at or past it and the run is TRUNCATED
+ * (offsets[j] is written iff j < offs_cap, a key byte iff its position is below data_cap; the call is
+ * still LSMB_OK, being asynchronous) — a caller tells by comparing its capacities with the totals.
+ * Asynchronous on `stream`, no host synchronisation inside.  LSMB_EINVAL, nothing written: the mark's
+ * conditions (the work buffer's size is the mark's to check), NULL d_key_data or d_key_offsets with a
+ * non-zero capacity, d_key_offsets misaligned. */
+int lsmb_compact_sst_gather_dev(lsmb_ctx* ctx, const void* d_bytes, uint64_t nbytes, uint64_t nblk,
+                                const uint64_t* blk_off, const uint32_t* blk_len, uint64_t nsrc, const uint64_t* sseg,
+                                const void* d_work, void* d_key_data, uint64_t data_cap, void* d_key_offsets,
+                                uint64_t offs_cap, void* stream);
+
+/* The output table's bloom block in one call, synchronous: host bytes in; upload, mark, the totals
+ * read back, lsmb_params(expected_items ? expected_items : max(survivors, 1), fpr), gather,
+ * lsmb_build_var_dev_new, BloomFilter::serialize into bloom[0 .. *bloom_len).  Replaces the
+ * MergeIterator walk of src/compaction/scheduler.rs:147-158 as far as the filter is concerned and
+ * SSTableBuilder's new / add per key / finish (src/sstable/builder.rs:74,93,177-182): expected_items
+ * = 1000, fpr = 0.01 reproduces the store's own block byte for byte; expected_items = 0 sizes the
+ * filter for the survivors.  *entry_count (may be NULL) = the survivors, the meta block's
+ * entry_count (builder.rs:90,139-162); *num_bits, *num_hashes (may be NULL) = the filter's shape.
+ * A bad block: LSMB_ECORRUPT, lsmb_last_error() names the source and the block, and no output is
+ * written.  Otherwise *bloom_len and the other outputs are always filled when the arguments pass;
+ * bloom == NULL or bloom_cap < *bloom_len is then LSMB_EINVAL, so a first call may ask for the
+ * size.  Zero survivors give the empty filter's block.  No host fallback: a NULL ctx is
+ * LSMB_EINVAL.  Other errors as lsmb_compact_sst_mark_dev (and lsmb_params' for fpr), with every
+ * output untouched. */
+int lsmb_compact_sst_bloom(lsmb_ctx* ctx, const uint8_t* bytes, uint64_t nbytes, uint64_t nblk,
+                           const uint64_t* blk_off, const uint32_t* blk_len, uint64_t nsrc, const uint64_t* sseg,
+                           int drop_tombstones, uint64_t expected_items, double false_positive_rate, uint8_t* bloom,
+                           uint64_t bloom_cap, uint64_t* bloom_len, uint64_t* entry_count, uint32_t* num_bits,
+                           uint32_t* num_hashes);
+
 /* CRC-32 of bloom blocks (optional checksum; the reference's
  * bloom block has none).  The same CRC as crc32fast::hash / zlib.crc32, which
  * the store already uses for WAL records and the manifest

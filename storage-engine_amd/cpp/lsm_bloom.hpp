@@ -158,6 +158,52 @@ class Context {
         return blocks;
     }
 
+    // The bloom block of the table a compaction of these data blocks writes
+    // (lsmb_compact_sst_bloom; run_compaction, src/compaction/scheduler.rs:
+    // 91-103,147-158): the blocks as above cut into sources, source s = the
+    // blocks [sseg[s], sseg[s+1]), source 0 the newest
+    // (src/iterator/merge.rs:15).  The newest version of each key survives,
+    // and with drop_tombstones (the task's is_bottommost) not the keys whose
+    // newest version is a tombstone.  expected_items = 0 sizes the filter for
+    // the survivors; 1000 with fpr 0.01 is SSTableBuilder's own
+    // (src/sstable/builder.rs:74).  A malformed or empty block throws
+    // Corruption naming it.  Always on the GPU.
+    struct CompactedFilter {
+        std::vector<uint8_t> bloom;  // BloomFilter::serialize's bytes
+        uint32_t num_bits = 0, num_hashes = 0;
+        uint64_t entry_count = 0;    // the meta block's (builder.rs:139-162)
+    };
+    CompactedFilter compact_sst_bloom(const std::vector<uint8_t>& bytes, const std::vector<uint64_t>& blk_off,
+                                      const std::vector<uint32_t>& blk_len, const std::vector<uint64_t>& sseg,
+                                      bool drop_tombstones, uint64_t expected_items = 0, double fpr = 0.01) {
+        if (sseg.empty() || blk_off.size() != blk_len.size())
+            throw std::invalid_argument("compact_sst_bloom: sseg needs nsrc + 1 entries, blk_off and blk_len one per block");
+        // a first size: the filter asked for, or one for every entry the blocks can hold without overlap
+        uint64_t guess = expected_items;
+        if (!guess) {
+            for (uint32_t l : blk_len) guess += l;
+            guess = guess / 6 ? guess / 6 : 1;
+        }
+        uint32_t nb = 0, k = 0;
+        check(lsmb_params(guess, fpr, &nb, &k));
+        CompactedFilter out;
+        uint64_t cap = lsmb_serialized_size(nb), len = 0;
+        const uint8_t none = 0;
+        int rc = LSMB_OK;
+        for (int pass = 0; pass < 2; pass++) {
+            out.bloom.assign(cap, 0);
+            rc = lsmb_compact_sst_bloom(c_, bytes.empty() ? &none : bytes.data(), bytes.size(), blk_off.size(), blk_off.data(),
+                                        blk_len.data(), sseg.size() - 1, sseg.data(), drop_tombstones ? 1 : 0,
+                                        expected_items, fpr, out.bloom.data(), cap, &len, &out.entry_count, &out.num_bits,
+                                        &out.num_hashes);
+            if (rc != LSMB_EINVAL || len <= cap) break;
+            cap = len;  // the block is larger than the guess (overlapping entries): once more
+        }
+        check(rc);
+        out.bloom.resize(len);
+        return out;
+    }
+
    private:
     lsmb_ctx* c_ = nullptr;
 };

@@ -140,7 +140,9 @@ constexpr uint64_t kDefaultHostMaxKeys = 2048;  // SST-size
 //    per slot, slots alternating by call.  The host waits for bb_done[s]
 //    before it refills slot s (two batches later), and a batch on another
 //    stream than the slot's last waits for it on its stream before the copy
-//    (bb_enqueue, capi_build_batch.hip).
+//    (bb_enqueue, capi_build_batch.hip).  The compaction calls stage their
+//    block descriptors through the same two slots under the same protocol
+//    (cs_enqueue, capi_compact.hip).
 // The host-side state itself is not locked: calls on one context come from
 // one thread at a time.
 struct lsmb_ctx {

@@ -170,6 +170,27 @@ hipError_t launch_build_batch_sst(const uint8_t* d_bytes, const SstBlk* d_blks, 
                                   uint32_t group_region32, uint32_t group_lanes, uint64_t* d_words,
                                   uint32_t* d_blk_entries, hipStream_t st, hipEvent_t done = nullptr);
 
+// The surviving keys of a compaction's merged data blocks (compact_sst.hip; the
+// contract, the descriptors and the work buffer's layout in sst_compact.hpp).
+// d_blks: the B claimed blocks, every one of them inside d_bytes (the caller
+// has checked); d_seg: the nsrc + 1 source bounds over them; d_work: 16-byte
+// aligned, lay.bytes long.  The mark writes the work buffer, d_totals[0 .. 4)
+// and, when d_blk_entries is non-null, d_blk_entries[b] for every claimed block;
+// the gather, after a mark of the same blocks on the same stream, writes
+// d_key_offsets[0 .. min(survivors + 1, offs_cap)) and the keys' bytes below
+// data_cap.  Nothing else is written; no host synchronisation.  stages (a
+// measurement's, tools/mb_compact_sst.py): 1 = the index pass alone, 2 = index
+// and mark, neither scans nor totals; 3 = the whole mark.
+struct CsBlk;
+struct CsLayout;
+hipError_t launch_compact_sst_mark(const uint8_t* d_bytes, const CsBlk* d_blks, const uint32_t* d_seg, uint32_t B,
+                                   const CsLayout& lay, int drop_tombstones, uint8_t* d_work, uint32_t* d_blk_entries,
+                                   uint64_t* d_totals, hipStream_t st, hipEvent_t done = nullptr, int stages = 3);
+hipError_t launch_compact_sst_gather(const uint8_t* d_bytes, const CsBlk* d_blks, uint32_t B, const CsLayout& lay,
+                                     const uint8_t* d_work, uint8_t* d_key_data, uint64_t data_cap,
+                                     uint64_t* d_key_offsets, uint64_t offs_cap, hipStream_t st,
+                                     hipEvent_t done = nullptr);
+
 // out[i] bit s = (lo_s <= key i <= hi_s) && may_contain(filter s, key i), for
 // the nfilt (<= 64) descriptors at d_filters (device memory).  One class
 // holding every descriptor takes the bit-sliced kernel with a compile-time

@@ -173,6 +173,14 @@ SIGNATURES = {
     "lsmb_build_batch_sst_blocks": (ctypes.c_int, [vp, u8p, ctypes.c_uint64, ctypes.c_uint64, u64p, u32p,
                                                    ctypes.c_uint64, u64p, u32p, u32p, u8p, ctypes.c_uint64, u64p, u64p,
                                                    ctypes.POINTER(ctypes.c_int32)]),
+    "lsmb_compact_sst_work_bytes": (ctypes.c_uint64, [ctypes.c_uint64, u32p]),
+    "lsmb_compact_sst_mark_dev": (ctypes.c_int, [vp, vp, ctypes.c_uint64, ctypes.c_uint64, u64p, u32p, ctypes.c_uint64,
+                                                 u64p, ctypes.c_int, vp, ctypes.c_uint64, vp, vp, vp]),
+    "lsmb_compact_sst_gather_dev": (ctypes.c_int, [vp, vp, ctypes.c_uint64, ctypes.c_uint64, u64p, u32p, ctypes.c_uint64,
+                                                   u64p, vp, vp, ctypes.c_uint64, vp, ctypes.c_uint64, vp]),
+    "lsmb_compact_sst_bloom": (ctypes.c_int, [vp, u8p, ctypes.c_uint64, ctypes.c_uint64, u64p, u32p, ctypes.c_uint64,
+                                              u64p, ctypes.c_int, ctypes.c_uint64, ctypes.c_double, u8p, ctypes.c_uint64,
+                                              u64p, u64p, u32p, u32p]),
     "lsmb_multi_open": (ctypes.c_int, [ctypes.POINTER(vp), ctypes.POINTER(ctypes.c_int), ctypes.c_int]),
     "lsmb_multi_close": (None, [vp]),
     "lsmb_multi_size": (ctypes.c_int, [vp]),
@@ -591,6 +599,89 @@ class Context:
         if rc != LSMB_ECORRUPT:
             _check(rc)
         return blooms[:int(boff[ntab])], boff, entries, status
+
+    # The surviving keys of a compaction's merged data blocks (src/iterator/merge.rs:98-121,
+    # src/compaction/scheduler.rs:147-158): the blocks as above, cut into sources, source s = the
+    # blocks [sseg[s], sseg[s+1]), source 0 the newest.
+    @staticmethod
+    def _compact_args(who, blk_off, blk_len, sseg):
+        bo = np.ascontiguousarray(blk_off, dtype=np.uint64)
+        bl = np.ascontiguousarray(blk_len, dtype=np.uint32)
+        sseg = np.ascontiguousarray(sseg, dtype=np.uint64)
+        if bo.size != bl.size:
+            raise ValueError("%s: blk_off and blk_len differ in length" % who)
+        if sseg.size < 1:
+            raise ValueError("%s: sseg needs nsrc + 1 entries" % who)
+        return bo, bl, sseg
+
+    def compact_sst_mark_dev(self, bytes, blk_off, blk_len, sseg, drop_tombstones, work, totals, blk_entries=None,
+                             stream=None):
+        """lsmb_compact_sst_mark_dev: bytes a uint8 device tensor holding the
+        blocks; blk_off, blk_len (nblk) and sseg (nsrc + 1) host sequences;
+        work a device tensor of at least compact_sst_work_bytes(blk_len)
+        bytes, 16-byte aligned; totals a device tensor of 4 int64 (survivors,
+        their key bytes, entries seen, bad blocks); blk_entries as
+        build_batch_sst_dev's.  Asynchronous on stream."""
+        bo, bl, sseg = self._compact_args("compact_sst_mark_dev", blk_off, blk_len, sseg)
+        if totals.numel() * totals.element_size() < 32:
+            raise ValueError("compact_sst_mark_dev: totals needs four uint64")
+        if blk_entries is not None and blk_entries.numel() * blk_entries.element_size() < 4 * bo.size:
+            raise ValueError("compact_sst_mark_dev: blk_entries needs one uint32 per block")
+        nblk = bo.size
+        _check(lib().lsmb_compact_sst_mark_dev(
+            self.h, vp(bytes.data_ptr()) if bytes is not None else None,
+            bytes.numel() * bytes.element_size() if bytes is not None else 0, nblk, _p(bo, u64p) if nblk else None,
+            _p(bl, u32p) if nblk else None, sseg.size - 1, _p(sseg, u64p), int(bool(drop_tombstones)),
+            vp(work.data_ptr()), work.numel() * work.element_size(),
+            vp(blk_entries.data_ptr()) if blk_entries is not None else None, vp(totals.data_ptr()),
+            self._stream(stream)))
+
+    def compact_sst_gather_dev(self, bytes, blk_off, blk_len, sseg, work, key_data, key_offsets, stream=None):
+        """lsmb_compact_sst_gather_dev after a mark of the same arguments on
+        the same stream: the survivors' keys into key_data (uint8 device
+        tensor, at least totals[1] bytes) and survivors + 1 offsets into
+        key_offsets (int64 device tensor).  Capacities below the mark's totals
+        truncate the run: nothing is written past them."""
+        bo, bl, sseg = self._compact_args("compact_sst_gather_dev", blk_off, blk_len, sseg)
+        nblk = bo.size
+        _check(lib().lsmb_compact_sst_gather_dev(
+            self.h, vp(bytes.data_ptr()) if bytes is not None else None,
+            bytes.numel() * bytes.element_size() if bytes is not None else 0, nblk, _p(bo, u64p) if nblk else None,
+            _p(bl, u32p) if nblk else None, sseg.size - 1, _p(sseg, u64p), vp(work.data_ptr()),
+            vp(key_data.data_ptr()) if key_data is not None and key_data.numel() else None,
+            key_data.numel() * key_data.element_size() if key_data is not None else 0,
+            vp(key_offsets.data_ptr()) if key_offsets is not None and key_offsets.numel() else None,
+            key_offsets.numel() * key_offsets.element_size() // 8 if key_offsets is not None else 0,
+            self._stream(stream)))
+
+    def compact_sst_bloom(self, bytes, blk_off, blk_len, sseg, drop_tombstones, expected_items=0, fpr=0.01):
+        """lsmb_compact_sst_bloom: host bytes holding the input tables' data
+        blocks -> (bloom block bytes, num_bits, k, entry_count) of the
+        compaction's output table.  expected_items = 0 sizes the filter for the
+        survivors; 1000 with fpr = 0.01 is the store's own block.  Corruption
+        for a malformed or empty block.  Runs on the GPU whatever the size."""
+        bo, bl, sseg = self._compact_args("compact_sst_bloom", blk_off, blk_len, sseg)
+        data = np.ascontiguousarray(np.frombuffer(bytes, dtype=np.uint8) if not isinstance(bytes, np.ndarray) else bytes,
+                                    dtype=np.uint8).reshape(-1)
+        nbytes, nblk = data.size, bo.size
+        if nbytes == 0:
+            data = np.zeros(1, np.uint8)
+        # a first size: the filter asked for, or one for every entry the blocks can hold without overlap
+        guess = int(expected_items) or max(int(bl.sum()) // 6, 1)
+        cap = serialized_size(params(guess, fpr)[0])
+        blen, count = ctypes.c_uint64(0), ctypes.c_uint64(0)
+        nb, k = ctypes.c_uint32(0), ctypes.c_uint32(0)
+        for _ in range(2):
+            bloom = np.empty(cap, dtype=np.uint8)
+            rc = lib().lsmb_compact_sst_bloom(
+                self.h, _p(data, u8p), nbytes, nblk, _p(bo, u64p) if nblk else None, _p(bl, u32p) if nblk else None,
+                sseg.size - 1, _p(sseg, u64p), int(bool(drop_tombstones)), int(expected_items), float(fpr),
+                _p(bloom, u8p), cap, ctypes.byref(blen), ctypes.byref(count), ctypes.byref(nb), ctypes.byref(k))
+            if rc != LSMB_EINVAL or blen.value <= cap:
+                break
+            cap = blen.value  # the block is larger than the guess (overlapping entries): once more
+        _check(rc)
+        return bloom[:blen.value].tobytes(), nb.value, k.value, count.value
 
     def probe_dev(self, filters, data, n, out, offsets=None, key_len=0, stream=None):
         """filters: [(words tensor on device, num_bits, k)]."""
@@ -1322,6 +1413,13 @@ def build_batch_parts(keys, num_bits):
 def build_batch_sst_parts(blocks, nbytes, num_bits):
     """Work items a batched build from data blocks gives one table of this shape (lsmb_build_batch_sst_parts)."""
     return int(lib().lsmb_build_batch_sst_parts(int(blocks), int(nbytes), int(num_bits)))
+
+
+def compact_sst_work_bytes(blk_len):
+    """Bytes of device work buffer compact_sst_mark_dev / compact_sst_gather_dev need for blocks of these lengths
+    (lsmb_compact_sst_work_bytes)."""
+    bl = np.ascontiguousarray(blk_len, dtype=np.uint32)
+    return int(lib().lsmb_compact_sst_work_bytes(bl.size, _p(bl, u32p) if bl.size else None))
 
 
 def crc32(data, crc=0):

@@ -23,6 +23,9 @@ filters for many such files straight from those bytes in one GPU call
 (lsmb_build_batch_sst_blocks) — what a saturated filter found by
 LevelSet.census, or a bloom block that failed its CRC, needs.  The blocks are
 parsed on the device; rewriting the file itself is not done here.
+`compact_filter` takes the input files of a compaction instead and returns the
+bloom block of its output table (lsmb_compact_sst_bloom): the newest version of
+each key, less the tombstones a bottommost compaction drops.
 """
 import io
 import os
@@ -270,3 +273,29 @@ def rebuild_filters(paths, fpr=0.01, ctx=None):
                              % (path, int(entries[t]), metas[t]["entry_count"]))
         out.append((blooms[int(boff[t]):int(boff[t + 1])].tobytes(), shapes[t][0], shapes[t][1], int(entries[t])))
     return out
+
+
+def compact_filter(paths_newest_first, drop_tombstones, fpr=0.01, expected_keys=None, ctx=None):
+    """The bloom block of the table a compaction of these files writes
+    (run_compaction, src/compaction/scheduler.rs:91-103,147-158), from their
+    data blocks in one lsmb_compact_sst_bloom call: the newest version of each
+    key survives (paths_newest_first[0] is source 0, src/iterator/merge.rs:15),
+    and with drop_tombstones (the task's is_bottommost) not the keys whose
+    newest version is a tombstone.  The filter is BloomFilter::new(expected_keys,
+    fpr) — 1000 and 0.01 give the store's own block (builder.rs:74) — or, with
+    expected_keys None, sized for the survivors.
+    -> (bloom block bytes, num_bits, k, entry_count).  Corruption when a block
+    is malformed or empty."""
+    ctx = ctx or default_context()
+    regions, offs, lens, sseg = [], [], [], [0]
+    base = 0
+    for path in paths_newest_first:
+        region, bo, bl, _ = read_blocks(path)
+        regions.append(region)
+        offs.append(bo + np.uint64(base))
+        lens.append(bl)
+        sseg.append(sseg[-1] + bo.size)
+        base += region.size
+    cat = lambda parts, dt: np.concatenate(parts) if parts else np.zeros(0, dt)  # noqa: E731
+    return ctx.compact_sst_bloom(cat(regions, np.uint8), cat(offs, np.uint64), cat(lens, np.uint32), sseg,
+                                 drop_tombstones, expected_items=int(expected_keys or 0), fpr=fpr)
