@@ -151,6 +151,63 @@ int stage_host_keys(lsmb_ctx* c, const uint8_t* data, const uint64_t* offsets, u
     return LSMB_OK;
 }
 
+int slot_enqueue(lsmb_ctx* c, SlotPart* parts, int nparts, hipStream_t st, const char* who, const char* what,
+                 const std::function<hipError_t(hipEvent_t done)>& launch) {
+    StagingSlots& sl = c->slots;
+    const auto up = [](size_t v) { return (v + kSlotAlign - 1) & ~(kSlotAlign - 1); };
+    size_t bytes = 0, at = 0;
+    for (int i = 0; i < nparts; i++) bytes = up(bytes) + parts[i].bytes;
+    const int s = sl.next;
+    sl.next ^= 1;
+    if (!sl.done[s])
+        HIP_TRY(hipEventCreateWithFlags(&sl.done[s], hipEventDisableTiming));
+    else if (sl.stream[s])
+        HIP_TRY(hipEventSynchronize(sl.done[s]));  // the copy out of this slot, two calls ago
+    if (int rc = pinned_ensure(c->pinned_retired, &sl.pin[s], &sl.pin_cap[s], bytes, who)) return rc;
+    HIP_TRY(sl.dev[s].ensure(bytes));
+    for (int i = 0; i < nparts; i++) {
+        at = up(at);
+        if (parts[i].bytes) memcpy(sl.pin[s] + at, parts[i].p, parts[i].bytes);
+        parts[i].d = (const uint8_t*)sl.dev[s].p + at;
+        at += parts[i].bytes;
+    }
+    if (sl.stream[s] && sl.stream[s] != st) HIP_TRY(hipStreamWaitEvent(st, sl.done[s], 0));
+    HIP_TRY(hipMemcpyAsync(sl.dev[s].p, sl.pin[s], bytes, hipMemcpyHostToDevice, st));
+    const hipError_t e = launch(sl.done[s]);
+    sl.stream[s] = st;
+    if (e == hipSuccess) return LSMB_OK;
+    (void)hipEventRecord(sl.done[s], st);  // (a failed launch may not have completed the event)
+    return hip_fail(e, what);
+}
+
+int claim_fail(const SstClaimFault& f, const SstClaim& cl, const char* who, const char* seg, const char* count,
+               const char* group, bool in_block) {
+    typedef unsigned long long ull;
+    const std::string of = in_block ? std::string(group) + " " + std::to_string(f.group) + ": " : std::string();
+    switch (f.rule) {
+        case kClaimOk: return LSMB_OK;
+        case kClaimGroupHook: return f.hook_rc;  // (the hook worded it)
+        case kClaimNullSeg: return fail(LSMB_EINVAL, "%s: null %s", who, seg);
+        case kClaimNullBlocks: return fail(LSMB_EINVAL, "%s: null blk_off or blk_len", who);
+        case kClaimGroups: return fail(LSMB_EINVAL, "%s: more than 2^31-1 %ss", who, group);
+        case kClaimSegDescends: return fail(LSMB_EINVAL, "%s: %s descends at %s %llu", who, seg, group, (ull)f.group);
+        case kClaimSegPast:
+            return fail(LSMB_EINVAL, "%s: %s[%s] = %llu is past the %llu blocks", who, seg, count, (ull)f.seg_end, (ull)cl.nblk);
+        case kClaimBlocks: return fail(LSMB_EINVAL, "%s: more than 2^31-1 blocks", who);
+        case kClaimBlockLeaves:
+            return fail(LSMB_EINVAL, "%s: %sblock %llu (%llu + %u) leaves the %llu bytes", who, of.c_str(), (ull)f.block,
+                        (ull)f.off, f.len, (ull)cl.nbytes);
+        case kClaimNullBytes: break;
+    }
+    return fail(LSMB_EINVAL, "%s: null bytes", who);
+}
+
+int stage_claim_span(lsmb_ctx* c, const uint8_t* bytes, SstSpan sp) {
+    HIP_TRY(c->keys.ensure(sp.hi - sp.lo + 16));
+    if (sp.hi > sp.lo) HIP_TRY(hipMemcpyAsync(c->keys.p, bytes + sp.lo, sp.hi - sp.lo, hipMemcpyHostToDevice, c->st));
+    return LSMB_OK;
+}
+
 int lists_to_host(uint64_t* starts, const uint64_t* d_starts, uint64_t last, uint32_t* index, const uint32_t* d_index,
                   uint64_t dcap, hipStream_t st) {
     HIP_TRY(hipMemcpyAsync(starts, d_starts, (last + 1) * 8, hipMemcpyDeviceToHost, st));
@@ -370,11 +427,7 @@ void lsmb_close(lsmb_ctx* c) {
         }
         if (c->cst) hipStreamDestroy(c->cst);
         if (c->pin_small) hipHostFree(c->pin_small);  // teardown
-        for (int s = 0; s < 2; s++) {
-            c->bb_items[s].release();
-            if (c->bb_pin[s]) hipHostFree(c->bb_pin[s]);  // teardown
-            if (c->bb_done[s]) hipEventDestroy(c->bb_done[s]);
-        }
+        c->slots.release();
         c->bb_words.release();
         if (c->bb_host) hipHostFree(c->bb_host);  // teardown
         c->pinned_retired.release();

@@ -11,7 +11,6 @@
 
 #include "build_batch_plan.hpp"
 #include "ctx.hpp"
-#include "sst_blocks.hpp"
 
 using namespace lsmb;
 
@@ -37,6 +36,18 @@ uint32_t bb_group_lanes() {
     return v >= kBbWaveLanes && v <= kBbGroupLanes && v % kBbWaveLanes == 0 ? (uint32_t)v : kBbGroupLanes;
 }
 
+// What every batched build asks of table t's filter; `hint` ends the message.
+int bb_check_table(const char* who, uint64_t t, uint32_t num_bits, uint32_t k, const char* hint) {
+    if (check_filter(num_bits, k) != LSMB_OK) {
+        const std::string msg = last_error();
+        return fail(LSMB_EINVAL, "%s: table %llu: %s", who, (unsigned long long)t, msg.c_str());
+    }
+    if (num_bits > kBbMaxBits)
+        return fail(LSMB_EINVAL, "%s: table %llu has %u bits, above lsmb_build_batch_max_bits() = %u%s", who,
+                    (unsigned long long)t, num_bits, kBbMaxBits, hint);
+    return LSMB_OK;
+}
+
 // What every batched build checks before anything is written.
 int bb_check(uint64_t n, uint64_t ntab, const uint64_t* seg, const uint32_t* num_bits, const uint32_t* num_hashes) {
     if (!seg || !num_bits || !num_hashes) return fail(LSMB_EINVAL, "batched build: null seg, num_bits or num_hashes");
@@ -45,15 +56,9 @@ int bb_check(uint64_t n, uint64_t ntab, const uint64_t* seg, const uint32_t* num
     for (uint64_t t = 0; t < ntab; t++) {
         if (seg[t + 1] < seg[t])
             return fail(LSMB_EINVAL, "batched build: seg descends at table %llu", (unsigned long long)t);
-        if (check_filter(num_bits[t], num_hashes[t]) != LSMB_OK) {
-            const std::string msg = last_error();
-            return fail(LSMB_EINVAL, "batched build: table %llu: %s", (unsigned long long)t, msg.c_str());
-        }
-        if (num_bits[t] > kBbMaxBits)
-            return fail(LSMB_EINVAL,
-                        "batched build: table %llu has %u bits, above lsmb_build_batch_max_bits() = %u "
-                        "(build it with lsmb_build_fixed_dev_new / lsmb_build_var_dev_new)",
-                        (unsigned long long)t, num_bits[t], kBbMaxBits);
+        if (int rc = bb_check_table("batched build", t, num_bits[t], num_hashes[t],
+                                    " (build it with lsmb_build_fixed_dev_new / lsmb_build_var_dev_new)"))
+            return rc;
         items += bb_parts(seg[t + 1] - seg[t], num_bits[t], bb_wave_max_bits());
     }
     if (seg[ntab] > n)
@@ -63,48 +68,18 @@ int bb_check(uint64_t n, uint64_t ntab, const uint64_t* seg, const uint32_t* num
     return LSMB_OK;
 }
 
-// The plan's items (and `tail`, further descriptors the launches read, behind
-// them) through a staging slot to the device and the launches, all on st;
-// nothing is synchronised but the slot's own reuse (see lsmb_ctx).
-// launch(d_items, d_tail, done) -> hipError_t enqueues the kernels.
-template <class Launch>
-int bb_enqueue_with(lsmb_ctx* c, const BbPlan& pl, const void* tail, size_t tail_bytes, hipStream_t st,
-                    const char* what, Launch&& launch) {
-    const size_t nz = pl.zero.size(), nw = pl.wave.size(), ng = pl.group.size();
-    const size_t ibytes = (nz + nw + ng) * sizeof(BbItem);  // (items are 64 B: the tail stays aligned)
-    const size_t bytes = ibytes + tail_bytes;
-    const int s = c->bb_slot;
-    c->bb_slot ^= 1;
-    if (!c->bb_done[s])
-        HIP_TRY(hipEventCreateWithFlags(&c->bb_done[s], hipEventDisableTiming));
-    else if (c->bb_stream[s])
-        HIP_TRY(hipEventSynchronize(c->bb_done[s]));  // the copy out of this slot, two batches ago
-    if (int rc = pinned_ensure(c->pinned_retired, &c->bb_pin[s], &c->bb_pin_cap[s], bytes, "batched build")) return rc;
-    HIP_TRY(c->bb_items[s].ensure(bytes));
-    BbItem* h = (BbItem*)c->bb_pin[s];
-    if (nz) memcpy(h, pl.zero.data(), nz * sizeof(BbItem));
-    if (nw) memcpy(h + nz, pl.wave.data(), nw * sizeof(BbItem));
-    if (ng) memcpy(h + nz + nw, pl.group.data(), ng * sizeof(BbItem));
-    if (tail_bytes) memcpy(c->bb_pin[s] + ibytes, tail, tail_bytes);
-    if (c->bb_stream[s] && c->bb_stream[s] != st) HIP_TRY(hipStreamWaitEvent(st, c->bb_done[s], 0));
-    HIP_TRY(hipMemcpyAsync(c->bb_items[s].p, h, bytes, hipMemcpyHostToDevice, st));
-    const uint8_t* d = (const uint8_t*)c->bb_items[s].p;
-    const hipError_t e = launch((const BbItem*)d, d + ibytes, c->bb_done[s]);
-    c->bb_stream[s] = st;
-    if (e != hipSuccess) {
-        (void)hipEventRecord(c->bb_done[s], st);  // (a failed launch may not have completed the event)
-        return hip_fail(e, what);
-    }
-    return LSMB_OK;
-}
+// The items through a staging slot to the device and the launches, all on st
+// (slot_enqueue, ctx.hpp).  The three lists are parts of whole 64-byte items, so
+// the device sees one array, zero items first, at the first part's address.
+static_assert(sizeof(BbItem) % kSlotAlign == 0, "the item lists are staged back to back");
 
 int bb_enqueue(lsmb_ctx* c, const KeyBatch& kb, const BbPlan& pl, uint64_t* d_words, hipStream_t st) {
-    return bb_enqueue_with(c, pl, nullptr, 0, st, "launch_build_batch",
-                           [&](const BbItem* d_items, const uint8_t*, hipEvent_t done) {
-                               return launch_build_batch(kb, d_items, (uint32_t)pl.zero.size(), (uint32_t)pl.wave.size(),
-                                                         (uint32_t)pl.group.size(), pl.wave_region32, pl.group_region32,
-                                                         bb_group_lanes(), d_words, st, done);
-                           });
+    SlotPart p[] = {slot_part(pl.zero), slot_part(pl.wave), slot_part(pl.group)};
+    return slot_enqueue(c, p, 3, st, "batched build", "launch_build_batch", [&](hipEvent_t done) {
+        return launch_build_batch(kb, (const BbItem*)p[0].d, (uint32_t)pl.zero.size(), (uint32_t)pl.wave.size(),
+                                  (uint32_t)pl.group.size(), pl.wave_region32, pl.group_region32, bb_group_lanes(),
+                                  d_words, st, done);
+    });
 }
 
 // ---- from data blocks (sst_blocks.hpp, build_batch_sst.hip) -----------------------
@@ -119,42 +94,16 @@ SstBounds bbs_bounds() {
     return bd;
 }
 
-// What lsmb_build_batch_sst_* check before anything is written or any of the
-// bytes is read; `bytes` is only compared with NULL.
-int bbs_check(const void* bytes, uint64_t nbytes, uint64_t nblk, const uint64_t* blk_off, const uint32_t* blk_len,
-              uint64_t ntab, const uint64_t* bseg, const uint32_t* num_bits, const uint32_t* num_hashes) {
-    if (!bseg || !num_bits || !num_hashes)
+// What lsmb_build_batch_sst_* check before anything is written or any byte is read:
+// sst_check_claim's rules (sst_blocks.hpp), table t's own in front of t's blocks.
+int bbs_check(const SstClaim& cl, const uint32_t* num_bits, const uint32_t* num_hashes) {
+    if (!cl.seg || !num_bits || !num_hashes)
         return fail(LSMB_EINVAL, "batched build from blocks: null bseg, num_bits or num_hashes");
-    if (nblk && (!blk_off || !blk_len)) return fail(LSMB_EINVAL, "batched build from blocks: null blk_off or blk_len");
-    if (ntab >= (1ull << 31)) return fail(LSMB_EINVAL, "batched build from blocks: more than 2^31-1 tables");
-    for (uint64_t t = 0; t < ntab; t++)
-        if (bseg[t + 1] < bseg[t])
-            return fail(LSMB_EINVAL, "batched build from blocks: bseg descends at table %llu", (unsigned long long)t);
-    if (bseg[ntab] > nblk)
-        return fail(LSMB_EINVAL, "batched build from blocks: bseg[ntab] = %llu is past the %llu blocks",
-                    (unsigned long long)bseg[ntab], (unsigned long long)nblk);
-    if (bseg[ntab] - bseg[0] >= (1ull << 31))
-        return fail(LSMB_EINVAL, "batched build from blocks: more than 2^31-1 blocks");
-    for (uint64_t t = 0; t < ntab; t++) {
-        if (check_filter(num_bits[t], num_hashes[t]) != LSMB_OK) {
-            const std::string msg = last_error();
-            return fail(LSMB_EINVAL, "batched build from blocks: table %llu: %s", (unsigned long long)t, msg.c_str());
-        }
-        if (num_bits[t] > kBbMaxBits)
-            return fail(LSMB_EINVAL,
-                        "batched build from blocks: table %llu has %u bits, above lsmb_build_batch_max_bits() = %u",
-                        (unsigned long long)t, num_bits[t], kBbMaxBits);
-        // the device never sees a block that leaves the buffer
-        for (uint64_t b = bseg[t]; b < bseg[t + 1]; b++) {
-            if (blk_off[b] > nbytes || blk_len[b] > nbytes - blk_off[b])
-                return fail(LSMB_EINVAL,
-                            "batched build from blocks: table %llu: block %llu (%llu + %u) leaves the %llu bytes",
-                            (unsigned long long)t, (unsigned long long)b, (unsigned long long)blk_off[b], blk_len[b],
-                            (unsigned long long)nbytes);
-            if (blk_len[b] && !bytes) return fail(LSMB_EINVAL, "batched build from blocks: null bytes");
-        }
-    }
-    return LSMB_OK;  // (a table has at most one part per block: fewer than 2^31 work items)
+    const char* who = "batched build from blocks";
+    const SstClaimFault f =
+        sst_check_claim(cl, [&](uint64_t t) { return bb_check_table(who, t, num_bits[t], num_hashes[t], ""); });
+    // (a table has at most one part per block: fewer than 2^31 work items)
+    return claim_fail(f, cl, who, "bseg", "ntab", "table", true);
 }
 
 // The claimed blocks [bseg[0], bseg[ntab]) renumbered from 0: their descriptors
@@ -179,13 +128,12 @@ BbsWork bbs_work(const uint64_t* blk_off, const uint32_t* blk_len, uint64_t ntab
 int bbs_enqueue(lsmb_ctx* c, const uint8_t* d_bytes, const BbsWork& w, uint64_t* d_words, uint32_t* d_blk_entries,
                 hipStream_t st) {
     const BbPlan& pl = w.pl;
-    return bb_enqueue_with(c, pl, w.blks.data(), w.blks.size() * sizeof(SstBlk), st, "launch_build_batch_sst",
-                           [&](const BbItem* d_items, const uint8_t* d_tail, hipEvent_t done) {
-                               return launch_build_batch_sst(
-                                   d_bytes, (const SstBlk*)d_tail, d_items, (uint32_t)pl.zero.size(),
-                                   (uint32_t)pl.wave.size(), (uint32_t)pl.group.size(), pl.wave_region32,
-                                   pl.group_region32, bb_group_lanes(), d_words, d_blk_entries, st, done);
-                           });
+    SlotPart p[] = {slot_part(pl.zero), slot_part(pl.wave), slot_part(pl.group), slot_part(w.blks)};
+    return slot_enqueue(c, p, 4, st, "batched build", "launch_build_batch_sst", [&](hipEvent_t done) {
+        return launch_build_batch_sst(d_bytes, (const SstBlk*)p[3].d, (const BbItem*)p[0].d, (uint32_t)pl.zero.size(),
+                                      (uint32_t)pl.wave.size(), (uint32_t)pl.group.size(), pl.wave_region32,
+                                      pl.group_region32, bb_group_lanes(), d_words, d_blk_entries, st, done);
+    });
 }
 
 static_assert(LSMB_SST_BAD_BLOCK == kSstBadBlock, "the header's value is the kernels'");
@@ -274,7 +222,7 @@ int lsmb_build_batch_sst_dev(lsmb_ctx* c, const void* d_bytes, uint64_t nbytes, 
                              void* stream) {
     if (!c) return fail(LSMB_EINVAL, "null ctx");
     if (ntab == 0) return LSMB_OK;
-    if (int rc = bbs_check(d_bytes, nbytes, nblk, blk_off, blk_len, ntab, bseg, num_bits, num_hashes)) return rc;
+    if (int rc = bbs_check(SstClaim{d_bytes, nbytes, nblk, blk_off, blk_len, ntab, bseg}, num_bits, num_hashes)) return rc;
     if (!d_words) return fail(LSMB_EINVAL, "batched build from blocks: null d_words");
     if (reinterpret_cast<uintptr_t>(d_words) & 15)
         return fail(LSMB_EINVAL, "batched build from blocks: d_words is not 16-byte aligned");
@@ -297,7 +245,8 @@ int lsmb_build_batch_sst_blocks(lsmb_ctx* c, const uint8_t* bytes, uint64_t nbyt
         bloom_off[0] = 0;
         return LSMB_OK;
     }
-    if (int rc = bbs_check(bytes, nbytes, nblk, blk_off, blk_len, ntab, bseg, num_bits, num_hashes)) return rc;
+    const SstClaim cl{bytes, nbytes, nblk, blk_off, blk_len, ntab, bseg};
+    if (int rc = bbs_check(cl, num_bits, num_hashes)) return rc;
     bloom_off[0] = 0;
     for (uint64_t t = 0; t < ntab; t++) bloom_off[t + 1] = bloom_off[t] + 12 + 8 * nwords64(num_bits[t]);
     if (!blooms || blooms_cap < bloom_off[ntab])
@@ -306,17 +255,10 @@ int lsmb_build_batch_sst_blocks(lsmb_ctx* c, const uint8_t* bytes, uint64_t nbyt
     DevGuard g(c->dev);
     // the bytes the claimed blocks span cross once, the blocks renumbered and rebased onto them
     const uint64_t b0 = bseg[0], nb = bseg[ntab] - b0;
-    uint64_t lo = nbytes, hi = 0;
-    for (uint64_t b = b0; b < b0 + nb; b++)
-        if (blk_len[b]) {
-            lo = std::min(lo, blk_off[b]);
-            hi = std::max(hi, blk_off[b] + blk_len[b]);
-        }
-    if (hi < lo) lo = hi = 0;
-    const BbsWork w = bbs_work(blk_off, blk_len, ntab, bseg, num_bits, num_hashes, lo);
+    const SstSpan sp = sst_claim_span(cl);
+    const BbsWork w = bbs_work(blk_off, blk_len, ntab, bseg, num_bits, num_hashes, sp.lo);
     const uint64_t wbytes = w.pl.word_off[ntab] * 8, obytes = wbytes + nb * 4;  // the words, then the blocks' counts
-    HIP_TRY(c->keys.ensure(hi - lo + 16));
-    if (hi > lo) HIP_TRY(hipMemcpyAsync(c->keys.p, bytes + lo, hi - lo, hipMemcpyHostToDevice, c->st));
+    if (int rc = stage_claim_span(c, bytes, sp)) return rc;
     HIP_TRY(c->bb_words.ensure(obytes));
     if (int rc = pinned_ensure(c->pinned_retired, &c->bb_host, &c->bb_host_cap, obytes, "batched build")) return rc;
     if (int rc = bbs_enqueue(c, (const uint8_t*)c->keys.p, w, (uint64_t*)c->bb_words.p,

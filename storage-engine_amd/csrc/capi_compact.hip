@@ -2,7 +2,6 @@
 // include/lsmbloom.h).  Host-side plumbing only; the contract, the plan and the
 // work buffer's layout are in sst_compact.hpp, the kernels in compact_sst.hip.
 #include <stdlib.h>
-#include <string.h>
 
 #include <algorithm>
 #include <vector>
@@ -14,28 +13,9 @@ using namespace lsmb;
 
 namespace {
 
-// What every lsmb_compact_sst_* call checks of the blocks and the sources before
-// anything is written or any of the bytes is read; `bytes` is only compared
-// with NULL.
-int cs_check(const void* bytes, uint64_t nbytes, uint64_t nblk, const uint64_t* blk_off, const uint32_t* blk_len,
-             uint64_t nsrc, const uint64_t* sseg) {
-    if (!sseg) return fail(LSMB_EINVAL, "compaction: null sseg");
-    if (nblk && (!blk_off || !blk_len)) return fail(LSMB_EINVAL, "compaction: null blk_off or blk_len");
-    if (nsrc >= (1ull << 31)) return fail(LSMB_EINVAL, "compaction: more than 2^31-1 sources");
-    for (uint64_t s = 0; s < nsrc; s++)
-        if (sseg[s + 1] < sseg[s]) return fail(LSMB_EINVAL, "compaction: sseg descends at source %llu", (unsigned long long)s);
-    if (sseg[nsrc] > nblk)
-        return fail(LSMB_EINVAL, "compaction: sseg[nsrc] = %llu is past the %llu blocks", (unsigned long long)sseg[nsrc],
-                    (unsigned long long)nblk);
-    if (sseg[nsrc] - sseg[0] >= (1ull << 31)) return fail(LSMB_EINVAL, "compaction: more than 2^31-1 blocks");
-    // the device never sees a block that leaves the buffer
-    for (uint64_t b = sseg[0]; b < sseg[nsrc]; b++) {
-        if (blk_off[b] > nbytes || blk_len[b] > nbytes - blk_off[b])
-            return fail(LSMB_EINVAL, "compaction: block %llu (%llu + %u) leaves the %llu bytes", (unsigned long long)b,
-                        (unsigned long long)blk_off[b], blk_len[b], (unsigned long long)nbytes);
-        if (blk_len[b] && !bytes) return fail(LSMB_EINVAL, "compaction: null bytes");
-    }
-    return LSMB_OK;
+// Before anything is written or any byte is read: sst_check_claim's rules (sst_blocks.hpp).
+int cs_check(const SstClaim& cl) {
+    return claim_fail(sst_check_claim(cl, [](uint64_t) { return 0; }), cl, "compaction", "sseg", "nsrc", "source", false);
 }
 
 int cs_check_work(const CsPlan& pl, const void* d_work, uint64_t work_bytes) {
@@ -45,37 +25,6 @@ int cs_check_work(const CsPlan& pl, const void* d_work, uint64_t work_bytes) {
     if (work_bytes < pl.lay.bytes)
         return fail(LSMB_EINVAL, "compaction: work_bytes %llu < the %llu bytes these blocks need (lsmb_compact_sst_work_bytes)",
                     (unsigned long long)work_bytes, (unsigned long long)pl.lay.bytes);
-    return LSMB_OK;
-}
-
-// The plan's block descriptors and source bounds through one of the batched
-// build's two staging slots to the device and the launches, all on st, under
-// that slot's protocol (lsmb_ctx, bb_enqueue_with of capi_build_batch.hip):
-// nothing is synchronised but the slot's own reuse.
-// launch(d_blks, d_seg, done) -> hipError_t enqueues the kernels.
-template <class Launch>
-int cs_enqueue(lsmb_ctx* c, const CsPlan& pl, hipStream_t st, const char* what, Launch&& launch) {
-    const size_t bbytes = pl.blks.size() * sizeof(CsBlk), sbytes = pl.seg.size() * sizeof(uint32_t);
-    const size_t bytes = bbytes + sbytes;  // (CsBlk is 24 B: the bounds behind them stay 4-byte aligned)
-    const int s = c->bb_slot;
-    c->bb_slot ^= 1;
-    if (!c->bb_done[s])
-        HIP_TRY(hipEventCreateWithFlags(&c->bb_done[s], hipEventDisableTiming));
-    else if (c->bb_stream[s])
-        HIP_TRY(hipEventSynchronize(c->bb_done[s]));  // the copy out of this slot, two calls ago
-    if (int rc = pinned_ensure(c->pinned_retired, &c->bb_pin[s], &c->bb_pin_cap[s], bytes, "compaction")) return rc;
-    HIP_TRY(c->bb_items[s].ensure(bytes));
-    if (bbytes) memcpy(c->bb_pin[s], pl.blks.data(), bbytes);
-    memcpy(c->bb_pin[s] + bbytes, pl.seg.data(), sbytes);
-    if (c->bb_stream[s] && c->bb_stream[s] != st) HIP_TRY(hipStreamWaitEvent(st, c->bb_done[s], 0));
-    HIP_TRY(hipMemcpyAsync(c->bb_items[s].p, c->bb_pin[s], bytes, hipMemcpyHostToDevice, st));
-    const uint8_t* d = (const uint8_t*)c->bb_items[s].p;
-    const hipError_t e = launch((const CsBlk*)d, (const uint32_t*)(d + bbytes), c->bb_done[s]);
-    c->bb_stream[s] = st;
-    if (e != hipSuccess) {
-        (void)hipEventRecord(c->bb_done[s], st);  // (a failed launch may not have completed the event)
-        return hip_fail(e, what);
-    }
     return LSMB_OK;
 }
 
@@ -89,19 +38,24 @@ int cs_stages() {
     return v == 1 || v == 2 ? v : 3;
 }
 
+// Both calls stage the block descriptors, then the source bounds (slot_enqueue, ctx.hpp).
 int cs_mark(lsmb_ctx* c, const uint8_t* d_bytes, const CsPlan& pl, int drop_tombstones, void* d_work,
             uint32_t* d_blk_entries, void* d_totals, hipStream_t st) {
-    return cs_enqueue(c, pl, st, "launch_compact_sst_mark", [&](const CsBlk* d_blks, const uint32_t* d_seg, hipEvent_t done) {
-        return launch_compact_sst_mark(d_bytes, d_blks, d_seg, (uint32_t)pl.blks.size(), pl.lay, drop_tombstones,
-                                       (uint8_t*)d_work, d_blk_entries, (uint64_t*)d_totals, st, done, cs_stages());
+    SlotPart p[] = {slot_part(pl.blks), slot_part(pl.seg)};
+    return slot_enqueue(c, p, 2, st, "compaction", "launch_compact_sst_mark", [&](hipEvent_t done) {
+        return launch_compact_sst_mark(d_bytes, (const CsBlk*)p[0].d, (const uint32_t*)p[1].d, (uint32_t)pl.blks.size(),
+                                       pl.lay, drop_tombstones, (uint8_t*)d_work, d_blk_entries, (uint64_t*)d_totals, st,
+                                       done, cs_stages());
     });
 }
 
 int cs_gather(lsmb_ctx* c, const uint8_t* d_bytes, const CsPlan& pl, const void* d_work, void* d_key_data,
               uint64_t data_cap, void* d_key_offsets, uint64_t offs_cap, hipStream_t st) {
-    return cs_enqueue(c, pl, st, "launch_compact_sst_gather", [&](const CsBlk* d_blks, const uint32_t*, hipEvent_t done) {
-        return launch_compact_sst_gather(d_bytes, d_blks, (uint32_t)pl.blks.size(), pl.lay, (const uint8_t*)d_work,
-                                         (uint8_t*)d_key_data, data_cap, (uint64_t*)d_key_offsets, offs_cap, st, done);
+    SlotPart p[] = {slot_part(pl.blks), slot_part(pl.seg)};
+    return slot_enqueue(c, p, 2, st, "compaction", "launch_compact_sst_gather", [&](hipEvent_t done) {
+        return launch_compact_sst_gather(d_bytes, (const CsBlk*)p[0].d, (uint32_t)pl.blks.size(), pl.lay,
+                                         (const uint8_t*)d_work, (uint8_t*)d_key_data, data_cap,
+                                         (uint64_t*)d_key_offsets, offs_cap, st, done);
     });
 }
 
@@ -119,7 +73,7 @@ int lsmb_compact_sst_mark_dev(lsmb_ctx* c, const void* d_bytes, uint64_t nbytes,
                               void* d_work, uint64_t work_bytes, void* d_blk_entries, void* d_totals, void* stream) {
     if (!c) return fail(LSMB_EINVAL, "null ctx");
     if (!d_totals) return fail(LSMB_EINVAL, "compaction: null d_totals");
-    if (int rc = cs_check(d_bytes, nbytes, nblk, blk_off, blk_len, nsrc, sseg)) return rc;
+    if (int rc = cs_check(SstClaim{d_bytes, nbytes, nblk, blk_off, blk_len, nsrc, sseg})) return rc;
     const CsPlan pl = cs_plan(blk_off, blk_len, nsrc, sseg, 0);
     if (int rc = cs_check_work(pl, d_work, work_bytes)) return rc;
     DevGuard g(c->dev);
@@ -132,7 +86,7 @@ int lsmb_compact_sst_gather_dev(lsmb_ctx* c, const void* d_bytes, uint64_t nbyte
                                 void* d_key_data, uint64_t data_cap, void* d_key_offsets, uint64_t offs_cap,
                                 void* stream) {
     if (!c) return fail(LSMB_EINVAL, "null ctx");
-    if (int rc = cs_check(d_bytes, nbytes, nblk, blk_off, blk_len, nsrc, sseg)) return rc;
+    if (int rc = cs_check(SstClaim{d_bytes, nbytes, nblk, blk_off, blk_len, nsrc, sseg})) return rc;
     const CsPlan pl = cs_plan(blk_off, blk_len, nsrc, sseg, 0);
     if (int rc = cs_check_work(pl, d_work, pl.lay.bytes)) return rc;  // (its size was the mark's to check)
     if ((data_cap && !d_key_data) || (offs_cap && !d_key_offsets))
@@ -151,22 +105,16 @@ int lsmb_compact_sst_bloom(lsmb_ctx* c, const uint8_t* bytes, uint64_t nbytes, u
     if (!bloom_len) return fail(LSMB_EINVAL, "compaction: null bloom_len");
     uint32_t nb = 0, k = 0;
     if (int rc = lsmb_params(expected_items ? expected_items : 1, fpr, &nb, &k)) return rc;
-    if (int rc = cs_check(bytes, nbytes, nblk, blk_off, blk_len, nsrc, sseg)) return rc;
+    const SstClaim cl{bytes, nbytes, nblk, blk_off, blk_len, nsrc, sseg};
+    if (int rc = cs_check(cl)) return rc;
     DevGuard g(c->dev);
     // the bytes the claimed blocks span cross once, the blocks rebased onto them
     const uint64_t b0 = sseg[0], B = sseg[nsrc] - b0;
-    uint64_t lo = nbytes, hi = 0;
-    for (uint64_t b = b0; b < b0 + B; b++)
-        if (blk_len[b]) {
-            lo = std::min(lo, blk_off[b]);
-            hi = std::max(hi, blk_off[b] + blk_len[b]);
-        }
-    if (hi < lo) lo = hi = 0;
-    const CsPlan pl = cs_plan(blk_off, blk_len, nsrc, sseg, lo);
+    const SstSpan sp = sst_claim_span(cl);
+    const CsPlan pl = cs_plan(blk_off, blk_len, nsrc, sseg, sp.lo);
     // the work buffer, then the totals, then the blocks' counts
     const uint64_t tot_at = (pl.lay.bytes + 15) & ~15ull, ent_at = tot_at + 32, wbytes = ent_at + B * 4;
-    HIP_TRY(c->keys.ensure(hi - lo + 16));
-    if (hi > lo) HIP_TRY(hipMemcpyAsync(c->keys.p, bytes + lo, hi - lo, hipMemcpyHostToDevice, c->st));
+    if (int rc = stage_claim_span(c, bytes, sp)) return rc;
     HIP_TRY(c->bb_words.ensure(wbytes));
     uint8_t* dw = (uint8_t*)c->bb_words.p;
     if (int rc = cs_mark(c, (const uint8_t*)c->keys.p, pl, drop_tombstones, dw, (uint32_t*)(dw + ent_at), dw + tot_at, c->st))

@@ -11,12 +11,14 @@
 #include <stdint.h>
 
 #include <algorithm>
+#include <functional>
 #include <string>
 #include <vector>
 
 #include "../../include/lsmbloom.h"
 #include "growbuf.hpp"
 #include "kernels.hpp"
+#include "sst_blocks.hpp"
 
 namespace lsmb {
 
@@ -100,6 +102,23 @@ inline int pinned_ensure(PinnedPool& pool, uint8_t** p, uint64_t* cap, uint64_t 
     return LSMB_OK;
 }
 
+// The two staging slots of slot_enqueue (below).
+struct StagingSlots {
+    uint8_t* pin[2] = {};
+    uint64_t pin_cap[2] = {};
+    DevBuf dev[2];
+    hipEvent_t done[2] = {};     // completed by the last launch of the slot's last call
+    hipStream_t stream[2] = {};  // stream of the slot's last call (nullptr: none yet)
+    int next = 0;                // alternates by call, whatever the route
+    void release() {
+        for (int s = 0; s < 2; s++) {
+            dev[s].release();
+            if (pin[s]) (void)hipHostFree(pin[s]);  // teardown
+            if (done[s]) (void)hipEventDestroy(done[s]);
+        }
+    }
+};
+
 inline uint64_t nwords64(uint32_t num_bits) { return ((uint64_t)num_bits + 63) / 64; }
 
 // The 12-byte header of BloomFilter::serialize (src/bloom/mod.rs:102-115).
@@ -136,13 +155,10 @@ constexpr uint64_t kDefaultHostMaxKeys = 2048;  // SST-size
 //    descriptors on another stream waits for it on that stream
 //    (probe_common, capi.hip).  Generic probes are thereby one chain in call
 //    order; bit-sliced probes read no descriptors and are not ordered.
-//  - batched-build items (bb_items[s], bb_pin[s]): bb_done[s] / bb_stream[s],
-//    per slot, slots alternating by call.  The host waits for bb_done[s]
-//    before it refills slot s (two batches later), and a batch on another
-//    stream than the slot's last waits for it on its stream before the copy
-//    (bb_enqueue, capi_build_batch.hip).  The compaction calls stage their
-//    block descriptors through the same two slots under the same protocol
-//    (cs_enqueue, capi_compact.hip).
+//  - staged work lists (slots.dev[s], slots.pin[s]): slots.done[s] /
+//    slots.stream[s], per slot, the two slots alternating by call and shared
+//    by the batched builds and the compaction calls.  The rules are stated
+//    once, at slot_enqueue (below; capi.hip).
 // The host-side state itself is not locked: calls on one context come from
 // one thread at a time.
 struct lsmb_ctx {
@@ -181,18 +197,7 @@ struct lsmb_ctx {
     uint8_t* pin_small = nullptr;  // pinned staging of small host builds (host_build_small)
     uint64_t pin_small_cap = 0;
     lsmb::PinnedPool pinned_retired;  // outgrown pinned staging, freed by lsmb_close
-    // batched builds (lsmb_build_batch_*): the work list crosses through one of
-    // two pinned staging slots into that slot's device copy, one async copy on
-    // the caller's stream.  bb_done[s] is completed by the last launch of the
-    // slot's last batch: the host waits for it before refilling the slot (two
-    // batches later), and a batch on another stream waits for it before its
-    // copy overwrites the device items, the way a build waits on ws_done.
-    uint8_t* bb_pin[2] = {nullptr, nullptr};
-    uint64_t bb_pin_cap[2] = {0, 0};
-    lsmb::DevBuf bb_items[2];
-    hipEvent_t bb_done[2] = {nullptr, nullptr};
-    hipStream_t bb_stream[2] = {nullptr, nullptr};  // stream of the slot's last batch (nullptr: none yet)
-    int bb_slot = 0;
+    lsmb::StagingSlots slots;  // work lists of lsmb_build_batch_* and lsmb_compact_sst_* (slot_enqueue)
     // lsmb_build_batch_blocks: the packed words on the device and, pinned, back on the host
     lsmb::DevBuf bb_words;
     uint8_t* bb_host = nullptr;
@@ -211,6 +216,32 @@ int stage_host_keys(lsmb_ctx* c, const uint8_t* data, const uint64_t* offsets, u
 inline bool host_keys_null(const uint8_t* data, const uint64_t* offsets, uint32_t key_len, uint64_t n) {
     return !data && (offsets ? offsets[n] > offsets[0] : key_len > 0);
 }
+
+// The staging-slot protocol.  slot_enqueue takes the next slot, waits on the
+// host for the slot's event (its last call, two calls ago), lays the host parts
+// into the pinned block, each on a 16-byte boundary (parts of whole 16 bytes lie
+// back to back), makes st wait for the event if the slot's last call was on
+// another stream, uploads the block on st and sets each part's device address.
+// launch(done) -> hipError_t then enqueues the kernels on st, the last of them
+// completing `done` itself; st becomes the slot's stream, and a failed launch
+// has the event recorded by hand and fails with `what`.  `who`: of LSMB_ENOMEM.
+constexpr size_t kSlotAlign = 16;
+struct SlotPart {
+    const void* p;
+    size_t bytes;
+    const uint8_t* d;  // out: where the part lies on the device
+};
+template <class T>
+SlotPart slot_part(const std::vector<T>& v) { return SlotPart{v.data(), v.size() * sizeof(T), nullptr}; }
+int slot_enqueue(lsmb_ctx* c, SlotPart* parts, int nparts, hipStream_t st, const char* who, const char* what,
+                 const std::function<hipError_t(hipEvent_t done)>& launch);
+
+// A block claim that sst_check_claim refused as the call's error, in the route's
+// words ("compaction", "sseg", "nsrc", "source"; in_block: "table T: " before
+// "block B"); a claim's span from host memory into c->keys, on c->st.
+int claim_fail(const SstClaimFault& f, const SstClaim& cl, const char* who, const char* seg, const char* count,
+               const char* group, bool in_block);
+int stage_claim_span(lsmb_ctx* c, const uint8_t* bytes, SstSpan sp);
 
 // The copy-back of every host lists probe (lsmb_fset_probe_lists,
 // lsmb_lset_probe_lists, lsmb_lset_probe_version_lists), in two steps on st:

@@ -1,7 +1,8 @@
 // sst_blocks.hpp — the store's data blocks as a key source of the batched build
 // (lsmb_build_batch_sst_*, kernels in build_batch_sst.hip).  The one statement
-// of the block format for the host and the device, the host plan of the blocks
-// route and the whole transform as plain C++ (build_batch_sst_ref).  No HIP
+// of the block format for the host and the device, the check of a caller's
+// claimed blocks, the host plan and the transform as plain C++ (sst_check_claim,
+// sst_plan, build_batch_sst_ref).  No HIP
 // calls and no kernels here, so that tests/cpp/sst_blocks_test.cpp can drive it
 // on a CPU.  Internal.
 //
@@ -147,6 +148,75 @@ inline BbPlan sst_plan(const uint32_t* blk_len, uint64_t ntab, const uint64_t* b
         for (uint64_t b = bseg[t]; b < bseg[t + 1]; b++) bytes += blk_len[b];
         return sst_parts(bseg[t + 1] - bseg[t], bytes, num_bits[t], bd);
     });
+}
+
+// ---- the caller's claim ------------------------------------------------------------------
+// What a call on blocks hands over: nblk blocks (blk_off, blk_len) of a buffer of
+// nbytes bytes, and seg[0 .. ngroups], which cuts the claimed blocks [seg[0],
+// seg[ngroups]) into groups (the build's tables, the compaction's sources).
+struct SstClaim {
+    const void* bytes;  // only ever compared with NULL here
+    uint64_t nbytes, nblk;
+    const uint64_t* blk_off;
+    const uint32_t* blk_len;
+    uint64_t ngroups;
+    const uint64_t* seg;
+};
+
+// The first rule a claim breaks, in the order of the checks, and what broke it:
+// `group`, seg_end = seg[ngroups], `block` with its (off, len), or the hook_rc
+// that the caller's own check of `group` gave.
+enum SstClaimRule { kClaimOk, kClaimNullSeg, kClaimNullBlocks, kClaimGroups, kClaimSegDescends, kClaimSegPast,
+                    kClaimBlocks, kClaimGroupHook, kClaimBlockLeaves, kClaimNullBytes };
+struct SstClaimFault {
+    SstClaimRule rule = kClaimOk;
+    uint64_t group = 0, block = 0, off = 0, seg_end = 0;
+    uint32_t len = 0;
+    int hook_rc = 0;
+};
+
+// The check behind every "no lane reads outside its block": after it, each
+// claimed block lies inside the nbytes and there are fewer than 2^31 groups and
+// claimed blocks.  Nothing is read before the rule that makes the read safe has
+// passed, and no block outside the claimed run is looked at.  per_group(g) -> int,
+// the caller's own rules, runs in front of g's blocks; non-zero ends the check.
+template <class PerGroup>
+inline SstClaimFault sst_check_claim(const SstClaim& cl, PerGroup&& per_group) {
+    SstClaimFault f;
+    const auto broke = [&f](SstClaimRule r) { return f.rule = r, f; };
+    if (!cl.seg) return broke(kClaimNullSeg);
+    if (cl.nblk && (!cl.blk_off || !cl.blk_len)) return broke(kClaimNullBlocks);
+    if (cl.ngroups >= (1ull << 31)) return broke(kClaimGroups);
+    for (f.group = 0; f.group < cl.ngroups; f.group++)
+        if (cl.seg[f.group + 1] < cl.seg[f.group]) return broke(kClaimSegDescends);
+    f.seg_end = cl.seg[cl.ngroups];
+    if (f.seg_end > cl.nblk) return broke(kClaimSegPast);
+    if (f.seg_end - cl.seg[0] >= (1ull << 31)) return broke(kClaimBlocks);
+    for (f.group = 0; f.group < cl.ngroups; f.group++) {
+        if ((f.hook_rc = per_group(f.group)) != 0) return broke(kClaimGroupHook);
+        for (f.block = cl.seg[f.group]; f.block < cl.seg[f.group + 1]; f.block++) {
+            f.off = cl.blk_off[f.block];
+            f.len = cl.blk_len[f.block];
+            if (f.off > cl.nbytes || f.len > cl.nbytes - f.off) return broke(kClaimBlockLeaves);
+            if (f.len && !cl.bytes) return broke(kClaimNullBytes);
+        }
+    }
+    return SstClaimFault();
+}
+
+// The bytes [lo, hi) that the non-empty claimed blocks of a checked claim span,
+// (0, 0) when there is none; `lo` is the `origin` of bbs_work / cs_plan.
+struct SstSpan {
+    uint64_t lo, hi;
+};
+inline SstSpan sst_claim_span(const SstClaim& cl) {
+    SstSpan sp{cl.nbytes, 0};
+    for (uint64_t b = cl.seg[0]; b < cl.seg[cl.ngroups]; b++)
+        if (cl.blk_len[b]) {
+            sp.lo = std::min(sp.lo, cl.blk_off[b]);
+            sp.hi = std::max(sp.hi, cl.blk_off[b] + cl.blk_len[b]);
+        }
+    return sp.hi < sp.lo ? SstSpan{0, 0} : sp;
 }
 
 // ---- the transform, serially ----------------------------------------------------------

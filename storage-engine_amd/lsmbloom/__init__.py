@@ -498,23 +498,27 @@ class Context:
     # Many SSTable filters from one key run (src/sstable/builder.rs:74,93,177-182
     # for every output table of src/compaction/scheduler.rs:147-177): table t =
     # BloomFilter::new + insert of keys [seg[t], seg[t+1]) of the run.
+    @staticmethod
+    def _table_args(who, seg, seg_name, num_bits, num_hashes):
+        # -> num_bits as an array and the C arguments ntab, seg, num_bits, num_hashes of every batched build
+        seg = np.ascontiguousarray(seg, dtype=np.uint64)
+        nb = np.ascontiguousarray(num_bits, dtype=np.uint32)
+        kk = np.ascontiguousarray(num_hashes, dtype=np.uint32)
+        if seg.size != nb.size + 1 or kk.size != nb.size:
+            raise ValueError("%s: %s needs ntab + 1 entries, num_hashes ntab" % (who, seg_name))
+        return nb, (nb.size, _p(seg, u64p), _p(nb, u32p) if nb.size else None, _p(kk, u32p) if nb.size else None)
+
     def build_batch_dev(self, data, n, seg, num_bits, num_hashes, words, offsets=None, key_len=0, stream=None):
         """lsmb_build_batch_dev: data (and offsets, n + 1 int64, for var-len
         keys) device tensors; seg (ntab + 1), num_bits and num_hashes (ntab)
         host sequences; words a 16-byte-aligned int64 device tensor of at least
         build_batch_layout(num_bits)[-1] words, output-only, in that layout.
         Asynchronous on stream.  Returns the layout (word_off, uint64)."""
-        seg = np.ascontiguousarray(seg, dtype=np.uint64)
-        nb = np.ascontiguousarray(num_bits, dtype=np.uint32)
-        kk = np.ascontiguousarray(num_hashes, dtype=np.uint32)
-        ntab = nb.size
-        if seg.size != ntab + 1 or kk.size != ntab:
-            raise ValueError("build_batch_dev: seg needs ntab + 1 entries, num_hashes ntab")
+        nb, tabs = self._table_args("build_batch_dev", seg, "seg", num_bits, num_hashes)
         _check(lib().lsmb_build_batch_dev(self.h, vp(data.data_ptr()) if data is not None else None,
                                           vp(offsets.data_ptr()) if offsets is not None else None, key_len, int(n),
-                                          ntab, _p(seg, u64p), _p(nb, u32p) if ntab else None,
-                                          _p(kk, u32p) if ntab else None, vp(words.data_ptr()),
-                                          words.numel() * words.element_size() // 8, self._stream(stream)))
+                                          *tabs, vp(words.data_ptr()), words.numel() * words.element_size() // 8,
+                                          self._stream(stream)))
         return build_batch_layout(nb)
 
     def build_batch_blocks(self, data, seg, num_bits, num_hashes, offsets=None, key_len=0):
@@ -523,33 +527,35 @@ class Context:
         (uint8) and their ntab + 1 offsets (uint64), the form
         lsmb_lset_add_batch takes.  Runs on the GPU whatever the key count."""
         data, n, op = _host_keys(data, offsets, key_len)
-        seg = np.ascontiguousarray(seg, dtype=np.uint64)
-        nb = np.ascontiguousarray(num_bits, dtype=np.uint32)
-        kk = np.ascontiguousarray(num_hashes, dtype=np.uint32)
-        ntab = nb.size
-        if seg.size != ntab + 1 or kk.size != ntab:
-            raise ValueError("build_batch_blocks: seg needs ntab + 1 entries, num_hashes ntab")
-        boff = np.zeros(ntab + 1, dtype=np.uint64)
+        nb, tabs = self._table_args("build_batch_blocks", seg, "seg", num_bits, num_hashes)
+        boff = np.zeros(nb.size + 1, dtype=np.uint64)
         blocks = np.empty(max(sum(serialized_size(int(b)) for b in nb), 1), dtype=np.uint8)
-        _check(lib().lsmb_build_batch_blocks(self.h, _p(data, u8p), op, key_len, n, ntab, _p(seg, u64p),
-                                             _p(nb, u32p) if ntab else None, _p(kk, u32p) if ntab else None,
-                                             _p(blocks, u8p), blocks.size, _p(boff, u64p)))
-        return blocks[:int(boff[ntab])], boff
+        _check(lib().lsmb_build_batch_blocks(self.h, _p(data, u8p), op, key_len, n, *tabs, _p(blocks, u8p), blocks.size,
+                                             _p(boff, u64p)))
+        return blocks[:int(boff[nb.size])], boff
 
     # The same filters straight from the tables' data blocks (src/sstable/block/builder.rs:40-76):
     # block b = bytes[blk_off[b] .. blk_off[b] + blk_len[b]), table t = blocks [bseg[t], bseg[t+1]).
     @staticmethod
-    def _sst_args(who, blk_off, blk_len, bseg, num_bits, num_hashes):
+    def _block_args(who, bytes, blk_off, blk_len, seg, seg_name):
+        # -> blk_off, blk_len and seg as arrays, and the five leading C arguments of every call on blocks;
+        # bytes is a device tensor, host bytes (empty ones become one zero byte, never a NULL pointer) or None
         bo = np.ascontiguousarray(blk_off, dtype=np.uint64)
         bl = np.ascontiguousarray(blk_len, dtype=np.uint32)
-        bseg = np.ascontiguousarray(bseg, dtype=np.uint64)
-        nb = np.ascontiguousarray(num_bits, dtype=np.uint32)
-        kk = np.ascontiguousarray(num_hashes, dtype=np.uint32)
+        seg = np.ascontiguousarray(seg, dtype=np.uint64)
         if bo.size != bl.size:
             raise ValueError("%s: blk_off and blk_len differ in length" % who)
-        if bseg.size != nb.size + 1 or kk.size != nb.size:
-            raise ValueError("%s: bseg needs ntab + 1 entries, num_hashes ntab" % who)
-        return bo, bl, bseg, nb, kk
+        if seg_name == "sseg" and seg.size < 1:  # (bseg is measured against num_bits, _table_args)
+            raise ValueError("%s: sseg needs nsrc + 1 entries" % who)
+        ptr, nbytes = None, 0
+        if hasattr(bytes, "data_ptr"):
+            ptr, nbytes = vp(bytes.data_ptr()), bytes.numel() * bytes.element_size()
+        elif bytes is not None:
+            data = bytes if isinstance(bytes, np.ndarray) else np.frombuffer(bytes, dtype=np.uint8)
+            data = np.ascontiguousarray(data, dtype=np.uint8).reshape(-1)
+            ptr, nbytes = _p(data if data.size else np.zeros(1, np.uint8), u8p), data.size  # (ptr keeps the array)
+        nblk = bo.size
+        return bo, bl, seg, (ptr, nbytes, nblk, _p(bo, u64p) if nblk else None, _p(bl, u32p) if nblk else None)
 
     def build_batch_sst_dev(self, bytes, blk_off, blk_len, bseg, num_bits, num_hashes, words, blk_entries=None,
                             stream=None):
@@ -559,15 +565,12 @@ class Context:
         blk_entries an int32 device tensor of nblk entries or None (entry b =
         block b's entry count, LSMB_SST_BAD_BLOCK for a malformed block).
         Asynchronous on stream.  Returns the layout (word_off, uint64)."""
-        bo, bl, bseg, nb, kk = self._sst_args("build_batch_sst_dev", blk_off, blk_len, bseg, num_bits, num_hashes)
+        bo, bl, bseg, head = self._block_args("build_batch_sst_dev", bytes, blk_off, blk_len, bseg, "bseg")
+        nb, tabs = self._table_args("build_batch_sst_dev", bseg, "bseg", num_bits, num_hashes)
         if blk_entries is not None and blk_entries.numel() * blk_entries.element_size() < 4 * bo.size:
             raise ValueError("build_batch_sst_dev: blk_entries needs one uint32 per block")
-        ntab, nblk = nb.size, bo.size
         _check(lib().lsmb_build_batch_sst_dev(
-            self.h, vp(bytes.data_ptr()) if bytes is not None else None,
-            bytes.numel() * bytes.element_size() if bytes is not None else 0, nblk, _p(bo, u64p) if nblk else None,
-            _p(bl, u32p) if nblk else None, ntab, _p(bseg, u64p), _p(nb, u32p) if ntab else None,
-            _p(kk, u32p) if ntab else None, vp(words.data_ptr()), words.numel() * words.element_size() // 8,
+            self.h, *head, *tabs, vp(words.data_ptr()), words.numel() * words.element_size() // 8,
             vp(blk_entries.data_ptr()) if blk_entries is not None else None, self._stream(stream)))
         return build_batch_layout(nb)
 
@@ -580,21 +583,15 @@ class Context:
         (that table's bloom bytes are unspecified, every other table's exact),
         and lsmb_last_error() names the first such table and block.  Runs on
         the GPU whatever the block count."""
-        bo, bl, bseg, nb, kk = self._sst_args("build_batch_sst_blocks", blk_off, blk_len, bseg, num_bits, num_hashes)
-        data = np.ascontiguousarray(np.frombuffer(bytes, dtype=np.uint8) if not isinstance(bytes, np.ndarray) else bytes,
-                                    dtype=np.uint8).reshape(-1)
-        nbytes = data.size
-        if nbytes == 0:
-            data = np.zeros(1, np.uint8)
-        ntab, nblk = nb.size, bo.size
+        bo, bl, bseg, head = self._block_args("build_batch_sst_blocks", bytes, blk_off, blk_len, bseg, "bseg")
+        nb, tabs = self._table_args("build_batch_sst_blocks", bseg, "bseg", num_bits, num_hashes)
+        ntab = nb.size
         boff = np.zeros(ntab + 1, dtype=np.uint64)
         blooms = np.empty(max(sum(serialized_size(int(b)) for b in nb), 1), dtype=np.uint8)
         entries = np.zeros(ntab, dtype=np.uint64)
         status = np.zeros(ntab, dtype=np.int32)
         rc = lib().lsmb_build_batch_sst_blocks(
-            self.h, _p(data, u8p), nbytes, nblk, _p(bo, u64p) if nblk else None, _p(bl, u32p) if nblk else None, ntab,
-            _p(bseg, u64p), _p(nb, u32p) if ntab else None, _p(kk, u32p) if ntab else None, _p(blooms, u8p), blooms.size,
-            _p(boff, u64p), _p(entries, u64p) if ntab else None,
+            self.h, *head, *tabs, _p(blooms, u8p), blooms.size, _p(boff, u64p), _p(entries, u64p) if ntab else None,
             _p(status, ctypes.POINTER(ctypes.c_int32)) if ntab else None)
         if rc != LSMB_ECORRUPT:
             _check(rc)
@@ -603,17 +600,6 @@ class Context:
     # The surviving keys of a compaction's merged data blocks (src/iterator/merge.rs:98-121,
     # src/compaction/scheduler.rs:147-158): the blocks as above, cut into sources, source s = the
     # blocks [sseg[s], sseg[s+1]), source 0 the newest.
-    @staticmethod
-    def _compact_args(who, blk_off, blk_len, sseg):
-        bo = np.ascontiguousarray(blk_off, dtype=np.uint64)
-        bl = np.ascontiguousarray(blk_len, dtype=np.uint32)
-        sseg = np.ascontiguousarray(sseg, dtype=np.uint64)
-        if bo.size != bl.size:
-            raise ValueError("%s: blk_off and blk_len differ in length" % who)
-        if sseg.size < 1:
-            raise ValueError("%s: sseg needs nsrc + 1 entries" % who)
-        return bo, bl, sseg
-
     def compact_sst_mark_dev(self, bytes, blk_off, blk_len, sseg, drop_tombstones, work, totals, blk_entries=None,
                              stream=None):
         """lsmb_compact_sst_mark_dev: bytes a uint8 device tensor holding the
@@ -622,16 +608,13 @@ class Context:
         bytes, 16-byte aligned; totals a device tensor of 4 int64 (survivors,
         their key bytes, entries seen, bad blocks); blk_entries as
         build_batch_sst_dev's.  Asynchronous on stream."""
-        bo, bl, sseg = self._compact_args("compact_sst_mark_dev", blk_off, blk_len, sseg)
+        bo, bl, sseg, head = self._block_args("compact_sst_mark_dev", bytes, blk_off, blk_len, sseg, "sseg")
         if totals.numel() * totals.element_size() < 32:
             raise ValueError("compact_sst_mark_dev: totals needs four uint64")
         if blk_entries is not None and blk_entries.numel() * blk_entries.element_size() < 4 * bo.size:
             raise ValueError("compact_sst_mark_dev: blk_entries needs one uint32 per block")
-        nblk = bo.size
         _check(lib().lsmb_compact_sst_mark_dev(
-            self.h, vp(bytes.data_ptr()) if bytes is not None else None,
-            bytes.numel() * bytes.element_size() if bytes is not None else 0, nblk, _p(bo, u64p) if nblk else None,
-            _p(bl, u32p) if nblk else None, sseg.size - 1, _p(sseg, u64p), int(bool(drop_tombstones)),
+            self.h, *head, sseg.size - 1, _p(sseg, u64p), int(bool(drop_tombstones)),
             vp(work.data_ptr()), work.numel() * work.element_size(),
             vp(blk_entries.data_ptr()) if blk_entries is not None else None, vp(totals.data_ptr()),
             self._stream(stream)))
@@ -642,12 +625,9 @@ class Context:
         tensor, at least totals[1] bytes) and survivors + 1 offsets into
         key_offsets (int64 device tensor).  Capacities below the mark's totals
         truncate the run: nothing is written past them."""
-        bo, bl, sseg = self._compact_args("compact_sst_gather_dev", blk_off, blk_len, sseg)
-        nblk = bo.size
+        bo, bl, sseg, head = self._block_args("compact_sst_gather_dev", bytes, blk_off, blk_len, sseg, "sseg")
         _check(lib().lsmb_compact_sst_gather_dev(
-            self.h, vp(bytes.data_ptr()) if bytes is not None else None,
-            bytes.numel() * bytes.element_size() if bytes is not None else 0, nblk, _p(bo, u64p) if nblk else None,
-            _p(bl, u32p) if nblk else None, sseg.size - 1, _p(sseg, u64p), vp(work.data_ptr()),
+            self.h, *head, sseg.size - 1, _p(sseg, u64p), vp(work.data_ptr()),
             vp(key_data.data_ptr()) if key_data is not None and key_data.numel() else None,
             key_data.numel() * key_data.element_size() if key_data is not None else 0,
             vp(key_offsets.data_ptr()) if key_offsets is not None and key_offsets.numel() else None,
@@ -660,12 +640,7 @@ class Context:
         compaction's output table.  expected_items = 0 sizes the filter for the
         survivors; 1000 with fpr = 0.01 is the store's own block.  Corruption
         for a malformed or empty block.  Runs on the GPU whatever the size."""
-        bo, bl, sseg = self._compact_args("compact_sst_bloom", blk_off, blk_len, sseg)
-        data = np.ascontiguousarray(np.frombuffer(bytes, dtype=np.uint8) if not isinstance(bytes, np.ndarray) else bytes,
-                                    dtype=np.uint8).reshape(-1)
-        nbytes, nblk = data.size, bo.size
-        if nbytes == 0:
-            data = np.zeros(1, np.uint8)
+        bo, bl, sseg, head = self._block_args("compact_sst_bloom", bytes, blk_off, blk_len, sseg, "sseg")
         # a first size: the filter asked for, or one for every entry the blocks can hold without overlap
         guess = int(expected_items) or max(int(bl.sum()) // 6, 1)
         cap = serialized_size(params(guess, fpr)[0])
@@ -674,8 +649,7 @@ class Context:
         for _ in range(2):
             bloom = np.empty(cap, dtype=np.uint8)
             rc = lib().lsmb_compact_sst_bloom(
-                self.h, _p(data, u8p), nbytes, nblk, _p(bo, u64p) if nblk else None, _p(bl, u32p) if nblk else None,
-                sseg.size - 1, _p(sseg, u64p), int(bool(drop_tombstones)), int(expected_items), float(fpr),
+                self.h, *head, sseg.size - 1, _p(sseg, u64p), int(bool(drop_tombstones)), int(expected_items), float(fpr),
                 _p(bloom, u8p), cap, ctypes.byref(blen), ctypes.byref(count), ctypes.byref(nb), ctypes.byref(k))
             if rc != LSMB_EINVAL or blen.value <= cap:
                 break

@@ -3,7 +3,9 @@
 // (src/sstable/block/builder.rs:40-76), the plan over runs of blocks and
 // build_batch_sst_ref, the serial statement of what the kernels of
 // build_batch_sst.hip do, against a literal per-key insert loop over the keys a
-// straightforward parser of its own extracts.  Every block under test lives in
+// straightforward parser of its own extracts; and the check of a caller's
+// claimed blocks with their span (sst_check_claim, sst_claim_span), rule by
+// rule, over arrays of exactly their length.  Every block under test lives in
 // a heap allocation of exactly its length, so one byte read past a block aborts
 // the program.  A stand-alone program (tests/test_build_batch_sst.py builds it
 // with -fsanitize=address,undefined and runs it).
@@ -312,7 +314,153 @@ static std::vector<Bytes> split(const std::vector<Entry>& es, size_t block_size)
     return out;
 }
 
+// ---- the caller's claim: sst_check_claim and sst_claim_span ---------------------------------
+// A claim whose three arrays live in heap allocations of exactly their length:
+// a read past blk_off[nblk - 1], blk_len[nblk - 1] or seg[ngroups] aborts the
+// program.  `bytes` is never dereferenced by the check, so any non-null
+// pointer stands for the buffer.
+struct Claim {
+    std::unique_ptr<uint64_t[]> off, seg;
+    std::unique_ptr<uint32_t[]> len;
+    SstClaim cl;
+};
+static const uint8_t g_some_byte = 0;
+static Claim claim(uint64_t nbytes, const std::vector<uint64_t>& off, const std::vector<uint32_t>& len,
+                   const std::vector<uint64_t>& seg) {
+    Claim c;
+    c.off.reset(new uint64_t[off.size()]);
+    c.len.reset(new uint32_t[len.size()]);
+    c.seg.reset(new uint64_t[seg.size()]);
+    std::copy(off.begin(), off.end(), c.off.get());
+    std::copy(len.begin(), len.end(), c.len.get());
+    std::copy(seg.begin(), seg.end(), c.seg.get());
+    c.cl = SstClaim{&g_some_byte, nbytes, off.size(), c.off.get(), c.len.get(), seg.size() - 1, c.seg.get()};
+    return c;
+}
+static SstClaimFault check(const SstClaim& cl) {
+    return sst_check_claim(cl, [](uint64_t) { return 0; });
+}
+
+static void check_claims() {
+    const uint64_t top = ~0ull;
+    // three blocks of a 100-byte buffer, two groups: accepted, the hook seen once per group in order
+    {
+        Claim c = claim(100, {0, 10, 50}, {10, 40, 50}, {0, 1, 3});
+        std::vector<uint64_t> seen;
+        const SstClaimFault f = sst_check_claim(c.cl, [&](uint64_t g) {
+            seen.push_back(g);
+            return 0;
+        });
+        CHECK(f.rule == kClaimOk && seen == std::vector<uint64_t>({0, 1}));
+        const SstSpan sp = sst_claim_span(c.cl);
+        CHECK(sp.lo == 0 && sp.hi == 100);
+    }
+    // each null array; blk_off and blk_len may be null when there is no block at all
+    {
+        Claim c = claim(100, {0, 10}, {10, 40}, {0, 1, 2});
+        SstClaim cl = c.cl;
+        cl.seg = nullptr;
+        CHECK(check(cl).rule == kClaimNullSeg);
+        cl = c.cl;
+        cl.blk_off = nullptr;
+        CHECK(check(cl).rule == kClaimNullBlocks);
+        cl = c.cl;
+        cl.blk_len = nullptr;
+        CHECK(check(cl).rule == kClaimNullBlocks);
+        Claim e = claim(100, {}, {}, {0, 0});
+        e.cl.blk_off = nullptr;
+        e.cl.blk_len = nullptr;
+        e.cl.bytes = nullptr;
+        CHECK(check(e.cl).rule == kClaimOk);
+        const SstSpan sp = sst_claim_span(e.cl);  // no claimed block
+        CHECK(sp.lo == 0 && sp.hi == 0);
+    }
+    // seg descends at group 1 of 3; the blocks are not looked at (block 0 leaves the buffer)
+    {
+        Claim c = claim(100, {90, 0, 0}, {20, 1, 1}, {0, 2, 1, 3});
+        const SstClaimFault f = check(c.cl);
+        CHECK(f.rule == kClaimSegDescends && f.group == 1);
+    }
+    // seg[ngroups] past nblk
+    {
+        Claim c = claim(100, {0, 10}, {10, 10}, {0, 1, 3});
+        const SstClaimFault f = check(c.cl);
+        CHECK(f.rule == kClaimSegPast && f.seg_end == 3);
+    }
+    // 2^31 groups over a valid 2-entry seg: refused before seg[2] would be read
+    {
+        Claim c = claim(100, {0}, {10}, {0, 1});
+        c.cl.ngroups = 1ull << 31;
+        CHECK(check(c.cl).rule == kClaimGroups);
+        c.cl.ngroups = top;
+        CHECK(check(c.cl).rule == kClaimGroups);
+    }
+    // a block that starts past the buffer; one that starts inside it and ends past it, the sum wrapping or not
+    {
+        Claim c = claim(100, {0, 101, 0}, {10, 0, 10}, {0, 1, 3});
+        SstClaimFault f = check(c.cl);
+        CHECK(f.rule == kClaimBlockLeaves && f.group == 1 && f.block == 1 && f.off == 101 && f.len == 0);
+        c = claim(100, {0, 100}, {10, 1}, {0, 2});
+        f = check(c.cl);
+        CHECK(f.rule == kClaimBlockLeaves && f.group == 0 && f.block == 1 && f.off == 100 && f.len == 1);
+        c = claim(100, {top}, {1}, {0, 1});
+        f = check(c.cl);
+        CHECK(f.rule == kClaimBlockLeaves && f.block == 0 && f.off == top);
+        c = claim(top, {top}, {1}, {0, 1});  // off <= nbytes, off + len wraps to 0
+        f = check(c.cl);
+        CHECK(f.rule == kClaimBlockLeaves && f.off == top && f.len == 1);
+        c = claim(100, {100, 99}, {0, 1}, {0, 2});  // the last byte and the empty block behind it are inside
+        CHECK(check(c.cl).rule == kClaimOk);
+    }
+    // a non-empty block with null bytes; empty blocks need no bytes
+    {
+        Claim c = claim(100, {0, 5}, {0, 1}, {0, 2});
+        c.cl.bytes = nullptr;
+        const SstClaimFault f = check(c.cl);
+        CHECK(f.rule == kClaimNullBytes && f.block == 1);
+        c = claim(100, {0, 5}, {0, 0}, {0, 2});
+        c.cl.bytes = nullptr;
+        CHECK(check(c.cl).rule == kClaimOk);
+    }
+    // the hook's refusal of group 1 comes before group 1's bad block and after group 0's good one
+    {
+        Claim c = claim(100, {0, 200}, {10, 1}, {0, 1, 2});
+        SstClaimFault f = sst_check_claim(c.cl, [](uint64_t g) { return g == 1 ? -7 : 0; });
+        CHECK(f.rule == kClaimGroupHook && f.group == 1 && f.hook_rc == -7);
+        f = check(c.cl);
+        CHECK(f.rule == kClaimBlockLeaves && f.group == 1 && f.block == 1);
+    }
+    // a strict sub-run claimed: the faults of blocks 0 and 4 are no one's business
+    {
+        Claim c = claim(100, {500, 10, 20, 30, top}, {9, 10, 10, 10, 9}, {1, 2, 4});
+        CHECK(check(c.cl).rule == kClaimOk);
+        const SstSpan sp = sst_claim_span(c.cl);
+        CHECK(sp.lo == 10 && sp.hi == 40);
+    }
+    // accepted: empty blocks at both ends of the claim; they do not widen the span
+    {
+        Claim c = claim(100, {0, 40, 60, 100}, {0, 5, 7, 0}, {0, 1, 4});
+        CHECK(check(c.cl).rule == kClaimOk);
+        const SstSpan sp = sst_claim_span(c.cl);
+        CHECK(sp.lo == 40 && sp.hi == 67);
+    }
+    // the span of only empty blocks, of one block, and of blocks out of address order
+    {
+        Claim c = claim(100, {30, 70}, {0, 0}, {0, 2});
+        SstSpan sp = sst_claim_span(c.cl);
+        CHECK(sp.lo == 0 && sp.hi == 0);
+        c = claim(100, {33}, {11}, {0, 1});
+        sp = sst_claim_span(c.cl);
+        CHECK(sp.lo == 33 && sp.hi == 44);
+        c = claim(100, {80, 3, 41}, {20, 5, 1}, {0, 1, 3});
+        CHECK(check(c.cl).rule == kClaimOk);
+        sp = sst_claim_span(c.cl);
+        CHECK(sp.lo == 3 && sp.hi == 100);
+    }
+}
+
 int main() {
+    check_claims();
     // ---- single blocks, well-formed: the counts, the odd keys and values, the long block
     for (size_t n : {0, 1, 63, 64, 65, 200}) check_block(encode_block(entries(n, 0, 3)), "n entries");
     check_block(encode_block({Entry("", "v"), Entry(rnd_str(300), "value"), Entry("k", "")}),

@@ -1,10 +1,11 @@
 """One context, several streams: the device entry points of lsmb_ctx take the
 caller's stream, and all of them share the context's build workspace (ws_*),
-its probe descriptor array (filt_desc) and the two item slots of the batched
-build (bb_items).  What keeps one stream's kernels from reading or overwriting
-what another stream's kernels still use is host-side bookkeeping (the table in
-csrc/ctx.hpp): ws_done / ws_stream, desc_done / desc_stream and bb_done /
-bb_stream.  A mistake there raises no error; it gives a filter with wrong words
+its probe descriptor array (filt_desc) and the two staging slots of the batched
+builds and the compaction calls (slots).  What keeps one stream's kernels from
+reading or overwriting what another stream's kernels still use is host-side
+bookkeeping (the table in csrc/ctx.hpp): ws_done / ws_stream, desc_done /
+desc_stream and slots.done / slots.stream.  A mistake there raises no error; it
+gives a filter with wrong words
 or a probe with wrong answers, and only when two streams overlap.
 
 Two kinds of test:
@@ -42,6 +43,8 @@ import pytest
 
 import keygen
 import lsmbloom
+import sst_support as ss
+from test_compact_sst import merge_model
 
 pytestmark = pytest.mark.gpu
 
@@ -604,7 +607,7 @@ def test_desc_sliced_probes_stay_independent(ctx, sliced, third):
         assert np.array_equal(got[3], p.ref[2])
 
 
-# ---------------------------------------------------------------- batched build (bb_done)
+# ---------------------------------------------------------------- batched build (slots.done)
 
 BB_COUNTS = (0, 1, 63, 64, 65, 1000)  # six SSTable filters of 0 .. 1000 keys
 BB_SEG = np.concatenate([[0], np.cumsum(BB_COUNTS)]).astype(np.uint64)
@@ -678,3 +681,108 @@ def test_bb_other_slot_runs_and_reused_slot_waits(ctx, oracle):
         b3.enqueue(ctx, s2)
     for i, b in enumerate((b1, b2, b3)):
         b.check(oracle, "batch %d" % (i + 1))
+
+
+# ---------------------------------------------------------------- the slots' three routes
+
+class _BlocksBatch:
+    """Three SSTable filters straight from seven data blocks of 1 .. 20 entries
+    at odd offsets, the middle table without a block."""
+    COUNTS = ((20, 1, 7), (), (13, 20, 2, 5))
+
+    def __init__(self, tag):
+        import torch
+        self.tables, first = [], 0
+        for counts in self.COUNTS:
+            self.tables.append([])
+            for c in counts:
+                self.tables[-1].append(ss.encode_block([(b"%04x-%08d" % (tag, first + i), b"v" * (i % 5))
+                                                        for i in range(c)]))
+                first += c
+        buf, self.blk_off, self.blk_len = ss.place([b for t in self.tables for b in t], odd=True)
+        assert all(int(o) % 2 for o in self.blk_off)
+        self.bseg = np.concatenate([[0], np.cumsum([len(t) for t in self.tables])]).astype(np.uint64)
+        self.bytes = torch.from_numpy(np.array(buf, dtype=np.uint8)).to(_dev())
+        self.nb, self.kk = [BB_SST[0]] * len(self.tables), [BB_SST[1]] * len(self.tables)
+        self.words = torch.full((int(lsmbloom.build_batch_layout(self.nb)[-1]),), -1, dtype=torch.int64, device=_dev())
+        self.ent = torch.full((len(self.blk_off),), -1, dtype=torch.int32, device=_dev())
+
+    def enqueue(self, ctx, s):
+        self.woff = ctx.build_batch_sst_dev(self.bytes, self.blk_off, self.blk_len, self.bseg, self.nb, self.kk,
+                                            self.words, blk_entries=self.ent, stream=s.cuda_stream)
+
+    def check(self, oracle, what):
+        got = _host(self.words)
+        nw = lsmbloom.num_words(BB_SST[0])
+        for t, blocks in enumerate(self.tables):
+            keys = [k for b in blocks for k in ss.parse_block(b)]
+            exp = oracle.build_var(*keygen.pack(keys), *BB_SST) if keys else np.zeros(nw, np.uint64)
+            _cmp(got[int(self.woff[t]):int(self.woff[t]) + nw], exp, "%s, table %d" % (what, t))
+        assert [int(e) for e in self.ent.cpu().numpy()] == [c for counts in self.COUNTS for c in counts], what
+
+
+class _Compaction:
+    """Two sources of two blocks each, drop_tombstones = 1: key 13 is in both
+    sources, key 2 is a tombstone in the newer one.  The outputs are sized from
+    the model, so that the gather can follow its mark with nothing in between."""
+
+    def __init__(self, tag):
+        import torch
+
+        def block(lo, n, tomb=None):
+            return ss.encode_block([(b"%04x-%08d" % (tag, i), b"" if i == tomb else b"val") for i in range(lo, lo + n)])
+
+        self.sources = [[block(0, 5, tomb=2), block(10, 4)], [block(5, 5), block(13, 6)]]  # newest first
+        buf, self.blk_off, self.blk_len = ss.place(self.sources[0] + self.sources[1], odd=True)
+        self.sseg = np.array([0, 2, 4], dtype=np.uint64)
+        self.exp, self.seen, bad, _ = merge_model(self.sources, 1)
+        assert len(self.exp) == 18 and self.seen == 20 and bad == 0  # 20 entries less the tombstone and the older 13
+        dev = _dev()
+        self.bytes = torch.from_numpy(np.array(buf, dtype=np.uint8)).to(dev)
+        self.work = torch.full((lsmbloom.compact_sst_work_bytes(self.blk_len),), 0xFF, dtype=torch.uint8, device=dev)
+        self.totals = torch.full((4,), -1, dtype=torch.int64, device=dev)
+        self.key_data = torch.full((sum(len(k) for k in self.exp),), 0xFF, dtype=torch.uint8, device=dev)
+        self.key_offs = torch.full((len(self.exp) + 1,), -1, dtype=torch.int64, device=dev)
+
+    def mark(self, ctx, s):
+        ctx.compact_sst_mark_dev(self.bytes, self.blk_off, self.blk_len, self.sseg, 1, self.work, self.totals,
+                                 stream=s.cuda_stream)
+
+    def gather(self, ctx, s):
+        ctx.compact_sst_gather_dev(self.bytes, self.blk_off, self.blk_len, self.sseg, self.work, self.key_data,
+                                   self.key_offs, stream=s.cuda_stream)
+
+    def check(self, what):
+        data, o = self.key_data.cpu().numpy().tobytes(), _host(self.key_offs)
+        assert [int(x) for x in _host(self.totals)] == [len(self.exp), len(data), self.seen, 0], what
+        assert [data[int(o[i]):int(o[i + 1])] for i in range(len(self.exp))] == self.exp, what
+
+
+def test_slots_shared_by_three_routes(ctx, oracle):
+    """The batched build, the build from blocks and the compaction's mark and
+    gather stage their work lists through the same two slots.  Eight calls on
+    two streams with no host synchronisation, each gather behind its own mark:
+    each slot is refilled by another route, from another stream, than its last
+    user's.  Every output starts as 0xFF and equals the oracle's filters or the
+    dict merge's survivors."""
+    import torch
+    s1, s2 = _streams(2)
+    a, b = _Batch(0xBD00), _Batch(0xBD01)
+    p, q = _BlocksBatch(0xBD02), _BlocksBatch(0xBD03)
+    m, n = _Compaction(0xBD04), _Compaction(0xBD05)
+    torch.cuda.synchronize()
+    with _synced(s1, s2):
+        a.enqueue(ctx, s1)
+        m.mark(ctx, s2)
+        p.enqueue(ctx, s1)
+        m.gather(ctx, s2)
+        b.enqueue(ctx, s2)
+        q.enqueue(ctx, s2)
+        n.mark(ctx, s1)
+        n.gather(ctx, s1)
+    a.check(oracle, "call 1, batched build")
+    b.check(oracle, "call 5, batched build")
+    p.check(oracle, "call 3, build from blocks")
+    q.check(oracle, "call 6, build from blocks")
+    m.check("calls 2 and 4, compaction")
+    n.check("calls 7 and 8, compaction")
